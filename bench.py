@@ -13,6 +13,10 @@ One rank per GPU (``python -m torch.distributed.run --nproc-per-node N bench.py 
 * W untimed warmup steps, then K timed steps bracketed by barrier + cuda synchronize;
   the reported value is aggregate (write+read) MiB/s over all ranks / max rank time.
 
+A plain run does only that. ``--full`` adds the secondary measurements after the timed steps
+(remote-client phase, volume roofline, stress-write, transport A/B); ``--dump-outputs DIR``
+saves what the last timed step's reads returned, from seeded payloads, as ``DIR/<name>.npy``.
+
 Per-GPU work is fixed as N grows ("weak" scaling). Durability defaults to nvme-sync:
 every replica's data and .meta are fdatasync'ed before the ack, like the reference.
 """
@@ -85,7 +89,62 @@ def parse():
                         "default 30, 4 with --cpu)")
     p.add_argument("--profile-dir", default=None,
                    help="run each ChunkServer under rocprofv3 --kernel-trace --stats, output here")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary measurements: the remote-client phase, "
+                        "the volume roofline, stress-write and the transport A/B (each with its own option "
+                        "above); without it a run only sets up, warms up, times the steps and reports")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, read back what the last timed step wrote and save it as "
+                        "DIR/<name>.npy (per file: size, CRC-32 of the whole content, and a fixed seeded "
+                        "sample of its bytes); payloads are seeded, so two builds can be compared")
+    p.add_argument("--seed", type=int, default=20240607, help="seed of the payloads and of the dumped sample")
+    a = p.parse_args()
+    if not a.full:
+        asked = [o for o, on in (("--remote-steps", a.remote_steps), ("--stress-seconds", a.stress_seconds > 0),
+                                 ("--roofline-records", a.roofline_records), ("--transport-ab", a.transport_ab == "on"))
+                 if on]
+        if asked:
+            p.error(f"{', '.join(asked)}: secondary measurements need --full")
+        a.remote_steps, a.roofline_records, a.stress_seconds, a.transport_ab = 0, 0, 0.0, "off"
+    return a
+
+
+DUMP_SAMPLE = 65536  # sampled byte offsets per file: 100 files -> 26 MB of float32
+
+
+def make_payloads(count: int, size: int, seed: int, rank: int) -> list[bytes]:
+    """Distinct random payloads, the same for the same arguments (generated outside any timed region)."""
+    import numpy as np
+
+    rng = np.random.default_rng([seed, rank, size])
+    return [rng.bytes(size) for _ in range(count)]
+
+
+def dump_outputs(out_dir: str, contents: list[bytes], seed: int, rank: int, world: int) -> None:
+    """What a reader of the last timed step's files received, as float arrays: every file's
+    size and CRC-32 (exact in float64), and its bytes at fixed seeded offsets (all of them for
+    files no longer than the sample)."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    per_file = max(1, min(DUMP_SAMPLE, (60 << 20) // 4 // max(1, len(contents))))
+    longest = max((len(c) for c in contents), default=0)
+    if longest <= per_file:
+        idx = np.arange(longest)
+    else:
+        idx = np.sort(np.random.default_rng([seed, longest]).choice(longest, size=per_file, replace=False))
+    sample = np.full((len(contents), len(idx)), -1.0, dtype=np.float32)  # -1: past the end of a short file
+    for i, c in enumerate(contents):
+        b = np.frombuffer(c, dtype=np.uint8)
+        ok = idx < len(b)
+        sample[i, ok] = b[idx[ok]]
+    sfx = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(out_dir, f"read_bytes_sample{sfx}.npy"), sample)
+    np.save(os.path.join(out_dir, f"read_sample_offsets{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, f"read_crc32{sfx}.npy"), np.array([zlib.crc32(c) for c in contents], dtype=np.float64))
+    np.save(os.path.join(out_dir, f"read_nbytes{sfx}.npy"), np.array([len(c) for c in contents], dtype=np.float64))
 
 
 def free_port() -> int:
@@ -200,10 +259,10 @@ def main():
         sys.exit(2)
     n = max(world, 1)
 
-    import torch
-    import torch.distributed as dist
-
     if world > 1:
+        import torch.distributed as dist
+
+
         # gloo prints its connection banner straight to fd 1; the driver reads exactly one
         # JSON line from rank 0's stdout, so keep the banner off it
         sys.stdout.flush()
@@ -393,7 +452,7 @@ def main():
 
             note("chunkserver up")
 
-            from rust_hadoop_generated_by_llm_amd.client.benchmark import bench_read, bench_write, make_payloads
+            from rust_hadoop_generated_by_llm_amd.client.benchmark import bench_read, bench_write
             from rust_hadoop_generated_by_llm_amd.client.client import Client
             from rust_hadoop_generated_by_llm_amd.models import proto as pb
             from rust_hadoop_generated_by_llm_amd.parallel.sharding import ShardMap
@@ -445,17 +504,20 @@ def main():
 
             client = Client([my_master], local_chunkserver=my_cs)
             client.set_shard_map(ShardMap.load_config_file(str(shard_file)))
-            payloads = make_payloads(a.count, a.size)
+            payloads = make_payloads(a.count, a.size, a.seed, rank)
             from concurrent.futures import ThreadPoolExecutor
 
             tpool = ThreadPoolExecutor(max_workers=a.concurrency, thread_name_prefix="bench")
 
-            def step(tag: str):
+            last_names: list = []  # the files of the most recent step (what --dump-outputs reads back)
+
+            def step(tag: str, keep: bool = False):
                 ws, names = bench_write(client, a.count, a.size, a.concurrency, prefix=prefix_of(rank),
                                         payloads=payloads, run_id=tag, pool=tpool)
                 verify = {nm: payloads[i % len(payloads)] for i, nm in enumerate(names)} if tag == "w0" else None
                 rs = bench_read(client, files=names, pool=tpool, verify=verify)
-                if reclaim_steps:
+                last_names[:] = names
+                if reclaim_steps and not keep:
                     list(tpool.map(client.delete_file, names))
                 return ws, rs
 
@@ -537,7 +599,7 @@ def main():
             wt = rt = 0.0
             slow: list = []  # the write tail: (ms, step, op, phase ms)
             for s in range(a.steps):
-                ws, rs = step(f"s{s}")
+                ws, rs = step(f"s{s}", keep=bool(a.dump_outputs) and s == a.steps - 1)
                 ph = getattr(ws, "op_phases", None) or []
                 slow += [(x, s, i, ph[i] if i < len(ph) else None) for i, x in enumerate(ws.latencies)]
                 slow = sorted(slow, key=lambda e: -e[0])[:20]
@@ -555,6 +617,10 @@ def main():
             end_sync_s = elapsed - t_loop
             gc.enable()
             note(f"{a.steps} timed steps in {elapsed:.3f} s")
+            if a.dump_outputs and not alt:
+                dump_outputs(a.dump_outputs, [client.get_file_content(nm) for nm in last_names], a.seed, rank, world)
+                if reclaim_steps:
+                    list(tpool.map(client.delete_file, last_names))
             cpu1 = cpu_snapshot()
             host_cpu = {k: round((cpu1[k] - cpu0.get(k, 0.0)) / elapsed, 2) for k in cpu1}
             job_cpu = cgroup_cpu_delta(cg0, cgroup_cpu(), elapsed)

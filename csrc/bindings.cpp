@@ -1,5 +1,6 @@
 // pybind11 module `_dfs_native`: the native data plane exposed to the service layer.
 // Every long-running call releases the GIL so gRPC worker threads run in parallel.
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -134,6 +135,19 @@ PYBIND11_MODULE(_dfs_native, m) {
     }
     return out;
   }, py::arg("src"), py::arg("offset"), py::arg("length"));
+  // host memory allocated pinned (hipHostMalloc), zeroed, as a numpy uint8 array that frees it
+  // with its last reference: what register_host takes on hosts that cannot pin memory a
+  // process already has
+  m.def("pinned_array", [](size_t nbytes) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, nbytes, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
+      (void)hipGetLastError();
+      throw std::runtime_error("hipHostMalloc failed");
+    }
+    std::memset(p, 0, nbytes);
+    py::capsule owner(p, [](void* q) { (void)hipHostFree(q); });
+    return py::array_t<uint8_t>({static_cast<py::ssize_t>(nbytes)}, static_cast<uint8_t*>(p), owner);
+  }, py::arg("nbytes"));
   m.def("crc32", [](py::buffer b, uint32_t crc) {
     py::buffer_info k;
     Buf v = view(b, k);

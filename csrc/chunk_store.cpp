@@ -16,6 +16,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
+#include <mutex>
+#include <set>
 #include <stdexcept>
 #include <unordered_map>
 
@@ -725,10 +727,33 @@ void ChunkStore::stage_slices_end(SliceStage* ss) {
   ss->ext = DevExtent{};
 }
 
+namespace {
+// Ranges handed to register_host that were allocated pinned (hipHostMalloc, a framework's pinned
+// allocator): device-visible as they are, owned by whoever allocated them, never unregistered here.
+std::mutex g_prepinned_mu;
+std::set<uintptr_t> g_prepinned;
+
+bool allocated_pinned(const void* p, uint64_t n) {
+  for (const uint8_t* q : {static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(p) + n - 1}) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, q) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    if (at.type != hipMemoryTypeHost) return false;
+  }
+  return true;
+}
+}  // namespace
+
 bool ChunkStore::register_host(const void* p, uint64_t n) {
   if (!gpu() || !p || !n) return false;
   HIP_OK(hipSetDevice(cfg_.device));
-  if (hipHostRegister(const_cast<void*>(p), n, hipHostRegisterDefault) != hipSuccess) {
+  if (host_registered(p, n)) return true;
+  if (allocated_pinned(p, n)) {
+    std::lock_guard<std::mutex> g(g_prepinned_mu);
+    g_prepinned.insert(reinterpret_cast<uintptr_t>(p));
+  } else if (hipHostRegister(const_cast<void*>(p), n, hipHostRegisterDefault) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
@@ -760,7 +785,12 @@ void ChunkStore::unregister_host(const void* p) {
   for (auto it = reg_.begin(); it != reg_.end(); ++it)
     if (it->first == reinterpret_cast<uintptr_t>(p)) {
       (void)hipSetDevice(cfg_.device);
-      (void)hipHostUnregister(const_cast<void*>(p));
+      bool ours;
+      {
+        std::lock_guard<std::mutex> pg(g_prepinned_mu);
+        ours = g_prepinned.erase(it->first) == 0;
+      }
+      if (ours) (void)hipHostUnregister(const_cast<void*>(p));
       reg_dev_.erase(reg_dev_.begin() + (it - reg_.begin()));
       reg_.erase(it);
       return;

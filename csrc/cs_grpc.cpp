@@ -89,7 +89,7 @@ class ReplyPool : public std::enable_shared_from_this<ReplyPool> {
         if (made_ >= kMax) return;
         ++made_;
       }
-      if (::posix_memalign(&p, 4096, kBytes) != 0) {
+      if (!(p = alloc())) {
         std::lock_guard<std::mutex> g(mu_);
         --made_;
         return;
@@ -98,6 +98,18 @@ class ReplyPool : public std::enable_shared_from_this<ReplyPool> {
       std::lock_guard<std::mutex> g(mu_);
       free_.push_back(static_cast<uint8_t*>(p));
     }
+  }
+
+  // Page-aligned and, next to a GPU store, allocated pinned (visible to every device of the
+  // process): not every host lets memory a process already has be pinned afterwards.
+  void* alloc() {
+    void* p = nullptr;
+    if (store_->gpu()) {
+      if (hipHostMalloc(&p, kBytes, hipHostMallocPortable | hipHostMallocMapped) == hipSuccess) return p;
+      (void)hipGetLastError();
+      p = nullptr;
+    }
+    return ::posix_memalign(&p, 4096, kBytes) == 0 ? p : nullptr;
   }
 
   std::shared_ptr<uint8_t> take() {
@@ -114,8 +126,8 @@ class ReplyPool : public std::enable_shared_from_this<ReplyPool> {
       }
     }
     if (!b) {
-      void* p = nullptr;
-      if (::posix_memalign(&p, 4096, kBytes) != 0) {
+      void* p = alloc();
+      if (!p) {
         std::lock_guard<std::mutex> g(mu_);
         --made_;
         return nullptr;

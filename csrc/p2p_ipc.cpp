@@ -137,7 +137,9 @@ struct RingMap {
   }
 };
 
-std::shared_ptr<RingMap> map_ring(const std::string& name, bool create, uint64_t gen, std::string* err) {
+// `need_dev`: the spin kernels poll and post the ring from the device; the event-driven modes
+// only touch it from the host, so there a ring that cannot be pinned is still a ring.
+std::shared_ptr<RingMap> map_ring(const std::string& name, bool create, uint64_t gen, bool need_dev, std::string* err) {
   const size_t bytes = (sizeof(IpcRing) + 4095) / 4096 * 4096;
   if (create) ::shm_unlink(name.c_str());
   int fd = ::shm_open(name.c_str(), create ? (O_RDWR | O_CREAT | O_EXCL) : O_RDWR, 0600);
@@ -184,8 +186,10 @@ std::shared_ptr<RingMap> map_ring(const std::string& name, bool create, uint64_t
     m->dev = static_cast<IpcRing*>(dev);
   } else {
     (void)hipGetLastError();
-    *err = "hipHostRegister of ring " + name + " failed";
-    return nullptr;
+    if (need_dev) {
+      *err = "hipHostRegister of ring " + name + " failed";
+      return nullptr;
+    }
   }
   return m;
 }
@@ -267,7 +271,7 @@ class IpcTransport final : public P2PTransport {
                                std::to_string(gen) + "_" + std::to_string(::getpid());
     std::vector<std::shared_ptr<RingMap>> rings;
     for (int c = 0; c < channels_; ++c) {
-      auto ring = map_ring(prefix + "_c" + std::to_string(c), true, gen, err);
+      auto ring = map_ring(prefix + "_c" + std::to_string(c), true, gen, spin_, err);
       if (!ring) return {};
       rings.push_back(ring);
     }
@@ -330,7 +334,7 @@ class IpcTransport final : public P2PTransport {
     for (int c = 0; c < channels_; ++c) {
       Lane& ln = *l.ch[c];
       ln.in = ins[c];
-      ln.out = map_ring(std::string(tw.ring) + "_c" + std::to_string(c), false, gen, err);
+      ln.out = map_ring(std::string(tw.ring) + "_c" + std::to_string(c), false, gen, spin_, err);
       if (!ln.out) return fail_open(l, err);
       for (hipStream_t* st : {&ln.send_stream, &ln.recv_stream})
         if (!*st && hipStreamCreateWithFlags(st, hipStreamNonBlocking) != hipSuccess) {

@@ -47,7 +47,7 @@ for step in "$@"; do
       run bench_a 600 python bench.py --steps 20 --warmup 5 && \
       run bench_b 600 python bench.py --steps 20 --warmup 5 || exit 1 ;;
     sustain)
-      run sustain 600 python bench.py --steps 5 --warmup 1 --remote-steps 0 --stress-seconds 6 \
+      run sustain 600 python bench.py --steps 5 --warmup 1 --full --remote-steps 0 --roofline-records 0 --stress-seconds 6 \
         --stress-size 1048576 --stress-concurrency 10 || exit 1 ;;
     exportab)
       DFS_EXPORT_MBPS=256 DFS_EXPORT_HEADROOM_MB=1 run export_active 600 python bench.py --steps 20 --warmup 5 && \

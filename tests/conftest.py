@@ -32,3 +32,20 @@ def has_gpu():
     from rust_hadoop_generated_by_llm_amd import native as n
 
     return n.gpu_count() > 0
+
+
+@pytest.fixture(scope="session")
+def can_pin_existing_memory(native, has_gpu, tmp_path_factory):
+    """Whether the GPU runtime can pin memory that was not allocated pinned, such as another
+    process's shared-memory arena (some hosts refuse it). Probed once with a small buffer."""
+    if not has_gpu:
+        return False
+    import numpy as np
+
+    store = native.ChunkStore(str(tmp_path_factory.mktemp("pinprobe")), "", 0, 64 << 20, 0, 100, 2, 1, False)
+    buf = np.zeros(1 << 16, dtype=np.uint8)
+    ok = bool(store.register_host(buf))
+    if ok:
+        store.unregister_host(buf)
+    del store
+    return ok

@@ -142,7 +142,7 @@ def test_native_writer_matches_python_writer(tmp_path):
     assert native(str(dirs["native"]), "--verify-chain", SECRET)[0] == 0
 
 
-def test_native_writer_ingest_and_drops(tmp_path):
+def test_native_writer_ingest_and_drops(tmp_path, monkeypatch):
     """Datagrams on the ingest socket are logged by the native thread; a full queue drops
     (never blocks) and counts it."""
     import socket
@@ -156,7 +156,9 @@ def test_native_writer_ingest_and_drops(tmp_path):
                            resource="r", status_code=200, error_code=None, user_agent=None, duration_ms=0))
     assert lg.m_dropped.get() == 12 and lg.m_total.get() == 20
     assert lg.flush(10)
-    path = str(tmp_path / "ingest.sock")
+    # a relative name: a socket address holds 107 bytes, less than a deep temporary directory's path
+    monkeypatch.chdir(tmp_path)
+    path = "ingest.sock"
     srv = socket.socket(socket.AF_UNIX, socket.SOCK_DGRAM)
     srv.bind(path)
     lg.start_ingest(srv)

@@ -43,10 +43,37 @@ def _check_common(d, n, steps, warmup):
 
 def test_bench_single_rank_cpu(tmp_path):
     d = _run([sys.executable, "bench.py", "--cpu", "--steps", "1", "--warmup", "1", "--count", "10",
-              "--remote-steps", "1"], tmp_path)
+              "--full", "--remote-steps", "1"], tmp_path)
     _check_common(d, 1, 1, 1)
     assert d["config"]["transport"] == "local"
     assert d["remote_client"]["native_client_ops"] == d["remote_client"]["steps"] * 2 * 10
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full only the headline is measured (no remote-client phase, no roofline), a
+    secondary option without --full is refused, and --dump-outputs writes what the last timed
+    step's reads returned: float arrays, identical from run to run (seeded payloads)."""
+    import numpy as np
+
+    outs = []
+    for k in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--cpu", "--steps", "2", "--warmup", "1", "--count", "6", "--size",
+                  "70001", "--dump-outputs", str(tmp_path / k)], tmp_path)
+        _check_common(d, 1, 2, 1)
+        assert "remote_client" not in d and "stress_write" not in d and "transport_ab" not in d
+        assert d["volume"]["roofline_mb_s"] == [None] and d["ms_per_step"] > 0
+        outs.append({f.name: np.load(f) for f in sorted((tmp_path / k).glob("*.npy"))})
+    a, b = outs
+    assert set(a) == {"read_bytes_sample.npy", "read_sample_offsets.npy", "read_crc32.npy", "read_nbytes.npy"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["read_bytes_sample.npy"].shape == (6, 65536) and (a["read_nbytes.npy"] == 70001).all()
+    assert 0 <= a["read_bytes_sample.npy"].min() and a["read_bytes_sample.npy"].max() == 255
+    assert len(set(a["read_crc32.npy"])) == 6  # distinct payloads
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    p = subprocess.run([sys.executable, "bench.py", "--cpu", "--steps", "1", "--remote-steps", "1"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--full" in p.stderr and not p.stdout.strip()
 
 
 @pytest.mark.parametrize("n", [4, 8])
@@ -153,7 +180,7 @@ def test_bench_transport_ab_block(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(TMPDIR=str(tmp_path))
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--cpu", "--steps", "2", "--warmup", "1",
-                        "--count", "8", "--remote-steps", "0", "--transport", "socket", "--transport-ab", "on"],
+                        "--count", "8", "--remote-steps", "0", "--transport", "socket", "--full", "--transport-ab", "on"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

@@ -47,10 +47,12 @@ def test_gpu_put_get_range_and_scrub(gpu_cluster):
     c.close()
 
 
-def test_gpu_fused_reads_local_and_remote(gpu_cluster):
+def test_gpu_fused_reads_local_and_remote(can_pin_existing_memory, gpu_cluster):
     """Reads land through the fused K3 verify+copy kernel: into the co-located client's
     registered shm slot, and into the native gRPC server's registered reply buffers for a
     client that is not co-located (every RPC over gRPC/TCP)."""
+    if not can_pin_existing_memory:
+        pytest.skip("the GPU runtime here cannot pin memory a process already has (hipHostRegister refused)")  # the co-located client's arena is another process's shared memory
     data = os.urandom((2 << 20) + 333)
     c = gpu_cluster.client(local_chunkserver=gpu_cluster.cs_addrs[0])
     c.create_file_from_buffer(data, "/gpu/fz")

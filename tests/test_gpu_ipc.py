@@ -81,8 +81,11 @@ def totals(c: LocalCluster):
 
 
 @pytest.mark.parametrize("mode", ["hipipc", "hipipc-push", "hipipc-spin"])
-def test_four_processes_one_gpu_crossing_traffic(mode):
+def test_four_processes_one_gpu_crossing_traffic(mode, request):
     from rust_hadoop_generated_by_llm_amd import native
+
+    if mode == "hipipc-spin" and native.gpu_count() >= 1 and not request.getfixturevalue("can_pin_existing_memory"):
+        pytest.skip("the GPU runtime here cannot pin memory a process already has (hipHostRegister refused)")  # the spin kernels poll a shared-memory ring from the device
 
     if native.gpu_count() < 1:
         pytest.fail("GPU test selected but no HIP device is visible")

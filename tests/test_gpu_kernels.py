@@ -356,6 +356,14 @@ def test_gpu_small_block_mirror(gstore):
     gstore.remove("mir")
 
 
+def _pinned_zeros(n):
+    """Host memory allocated pinned, as a numpy array (memory a process already has cannot be
+    pinned afterwards on every host); freed with the array's last reference."""
+    from rust_hadoop_generated_by_llm_amd import native
+
+    return native.lib.pinned_array(n)
+
+
 def test_gpu_fused_write_copy(gstore):
     """K1/K2 fused with the host-to-device copy (crc_write_copy_kernel): a write whose bytes sit
     in registered host memory is one kernel that stores the block into HBM, checksums it and
@@ -363,7 +371,7 @@ def test_gpu_fused_write_copy(gstore):
     and a wrong expected CRC still rejected. Blocks <= 64 KiB keep the host-CRC path."""
     import numpy as np
 
-    buf = np.zeros((40 << 20) + 4096, dtype=np.uint8)
+    buf = _pinned_zeros((40 << 20) + 4096)
     assert gstore.register_host(buf)
     try:
         f0 = gstore.stats()["fused_writes"]
@@ -401,7 +409,7 @@ def test_gpu_fused_read_copy(gstore):
     must still be reported; bytes outside the range are never written."""
     import numpy as np
 
-    buf = np.zeros((40 << 20) + 4096, dtype=np.uint8)
+    buf = _pinned_zeros((40 << 20) + 4096)
     assert gstore.register_host(buf)
     try:
         sizes = [(1 << 20), (1 << 20) + 777, 300000, 3 * (1 << 20) + 1, (33 << 20) + 512 * 3 + 5]

@@ -944,9 +944,13 @@ def test_gateway_workers_share_one_audit_chain(cluster, tmp_path, front):
     """S3_WORKERS=3: three processes accept on one socket; every worker's audit records
     reach worker 0's logger, so the store holds ONE verifiable hash chain with all of them."""
     audit_dir = tmp_path / "audit"
+    # slots at test scale (the bodies here are under 100 bytes): every worker populates its whole
+    # shared-memory arena before it serves, 3 x 2 GiB at the defaults, and a worker still doing
+    # that does not see the SIGTERM at the end
     url = cluster.start_s3({"S3_WORKERS": "3", "S3_AUTH_ENABLED": "true", "S3_ACCESS_KEY": "admin",
                             "S3_SECRET_KEY": "admin-secret", "AUDIT_LOG_DIR": str(audit_dir),
                             "AUDIT_HMAC_SECRET": AUDIT_SECRET, "AUDIT_LOG_BATCH_SIZE": "1",
+                            "S3_FRONT_SLOTS": "4", "S3_FRONT_SLOT_MB": "8",
                             **_front_env(cluster, front)}, name="s3w")
     pr = next(p for p in cluster.procs if p.name == "s3w")
     assert pr.info.get("workers") == 3

@@ -503,8 +503,89 @@ static void roofline(const std::string& dir, int threads, int per) {
               "\"p99_ms\": %.3f}\n", mbps, threads, lat.size(), secs_total, pct(0.5), pct(0.99));
 }
 
+// --ec-fused: ChunkStore::ec_encode of a stripe in registered memory, the single-kernel path
+// against the staged one (copies, K4, one K2 launch per shard), alternating in every repetition.
+// One JSON line per (k, m, shard length) cell; times are microseconds per stripe, each the mean
+// of `iters` back-to-back encodes (every encode ends in a stream synchronise).
+static int ec_fused_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--ec-fused needs a GPU\n");
+    return 1;
+  }
+  std::filesystem::remove_all(dir);
+  StoreConfig cfg;
+  cfg.storage_dir = dir + "/ecf";
+  cfg.device = device;
+  cfg.hbm_capacity = 2ull << 30;
+  ChunkStore s(cfg);
+  const int shapes[][2] = {{4, 2}, {6, 3}, {10, 4}};
+  int rc = 0;
+  for (auto& km : shapes)
+    for (uint64_t len : {256ull << 10, 1ull << 20, 16ull << 20}) {
+      const int k = km[0], m = km[1];
+      uint8_t* buf = nullptr;
+      if (hipHostMalloc(reinterpret_cast<void**>(&buf), k * len, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
+        return 1;
+      const auto data = random_bytes(k * len, static_cast<uint32_t>(k * 131 + len));
+      std::memcpy(buf, data.data(), data.size());
+      s.register_host(buf, k * len);
+      gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+      const int iters = static_cast<int>(std::clamp<uint64_t>((256ull << 20) / (k * len), 3, 100));
+      std::vector<uint32_t> crcs[2];
+      std::vector<double> us[2];  // [0] staged, [1] fused
+      bool ok = true;
+      auto run = [&](int fused, int n) {
+        set_ec_fused(fused != 0);
+        const auto t0 = Clock::now();
+        for (int i = 0; i < n && ok; ++i) {
+          ChunkStore::EcBuffers enc;
+          std::string err;
+          ok = s.ec_encode(buf, len, len, k, parity, &enc, &err);
+          if (ok) crcs[fused] = enc.crc;
+          s.ec_free(&enc);
+        }
+        return secs(t0, Clock::now()) * 1e6 / n;
+      };
+      for (int fused = 0; fused < 2; ++fused) run(fused, 2);  // warm-up: code objects, scratch, extents
+      const uint64_t before = s.stats().ec_fused_encodes;
+      for (int rep = 0; rep < reps; ++rep)
+        for (int fused = 1; fused >= 0; --fused) us[fused].push_back(run(fused, iters));
+      const uint64_t fused_runs = s.stats().ec_fused_encodes - before;
+      auto list = [](const std::vector<double>& v) {
+        std::string o;
+        for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+        return o;
+      };
+      const bool match = ok && crcs[0] == crcs[1] && fused_runs == static_cast<uint64_t>(reps) * iters;
+      std::printf("{\"ec_fused\": {\"k\": %d, \"m\": %d, \"shard_len\": %llu, \"iters\": %d, \"fused_us\": [%s], "
+                  "\"staged_us\": [%s], \"fused_min_us\": %.1f, \"staged_min_us\": %.1f, \"match\": %s}}\n",
+                  k, m, static_cast<unsigned long long>(len), iters, list(us[1]).c_str(), list(us[0]).c_str(),
+                  *std::min_element(us[1].begin(), us[1].end()), *std::min_element(us[0].begin(), us[0].end()),
+                  match ? "true" : "false");
+      std::fflush(stdout);
+      if (!match) rc = 1;
+      s.unregister_host(buf);
+      (void)hipHostFree(buf);
+    }
+  set_ec_fused(true);
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 int main(int argc, char** argv) {
   dfs::trace_init();  // before any thread: roctx's first range calls setenv (trace.h)
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--ec-fused") {
+      std::string dir = "/tmp/io_bench_ecf";
+      int device = 0, reps = 3;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return ec_fused_bench(device, dir, std::max(1, reps));
+    }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--md5") {
       int conc = 10, per = 20;

@@ -59,6 +59,26 @@ py::bytes meta_image(const std::vector<uint32_t>& v) {
   return out;
 }
 
+// Device EC results as [(shard bytes, whole-shard CRC-32, .meta image)]; frees the buffers.
+py::object ec_result(ChunkStore& s, ChunkStore::EcBuffers* b) {
+  const uint64_t mbytes = num_slices(b->len) * 4;
+  py::list out;
+  bool ok = true;
+  for (int i = 0; i < b->count; ++i) {
+    char *d, *md;
+    py::bytes shard = new_bytes(b->len, &d), meta = new_bytes(mbytes, &md);
+    {
+      py::gil_scoped_release rel;
+      ok = ok && s.device_to_host(reinterpret_cast<uint8_t*>(d), b->shard(i), b->len) &&
+           s.device_to_host(reinterpret_cast<uint8_t*>(md), b->meta(i), mbytes);
+    }
+    out.append(py::make_tuple(shard, b->crc[i], meta));
+  }
+  s.ec_free(b);
+  if (!ok) throw std::runtime_error("device EC: reading the shards back failed");
+  return out;
+}
+
 gf::Matrix to_matrix(const std::vector<std::vector<int>>& m) {
   gf::Matrix out;
   for (auto& row : m) {
@@ -223,6 +243,7 @@ PYBIND11_MODULE(_dfs_native, m) {
   m.def("crc_wide_mode", &crc_wide_mode);
   m.def("crc_fp4_enabled", &crc_fp4_enabled);
   m.def("set_crc_fp4", &set_crc_fp4, "wide K1/K2: chunk CRCs on the FP4 matrix cores (else i8)");
+  m.def("set_ec_fused", &set_ec_fused, "device EC in one fused kernel per stripe (else copies, K4/K5, K2 per shard)");
   m.def("set_crc_wide", &set_crc_wide, "K1/K2 one workgroup per CU: 0 off, 1 shared LDS image, 2 + LDS basis");
   m.def("set_crc_kernels", [](bool mfma, int scrub_ring, int tile_ring) {
     set_crc_mfma(mfma);
@@ -436,7 +457,52 @@ PYBIND11_MODULE(_dfs_native, m) {
         }
         if (!ok) return py::none();
         return py::cast(outs);
-      });
+      })
+      // device-resident RS: the k data shards of `buf` (stride apart; registered memory takes
+      // the single-kernel path) plus m parity shards, as [(shard, crc32, .meta image)]
+      .def("ec_encode", [](ChunkStore& s, py::buffer buf, int k, int m, uint64_t shard_len, uint64_t stride) -> py::object {
+        py::buffer_info keep;
+        Buf v = view(buf, keep);
+        if (k <= 0 || m <= 0 || shard_len == 0 || stride < shard_len || v.n < stride * (k - 1) + shard_len)
+          throw std::invalid_argument("ec_encode: buffer shorter than k shards at this stride");
+        gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+        ChunkStore::EcBuffers enc;
+        std::string err;
+        bool ok;
+        {
+          py::gil_scoped_release rel;
+          ok = s.ec_encode(v.p, stride, shard_len, k, parity, &enc, &err);
+        }
+        if (!ok) return py::none();
+        return ec_result(s, &enc);
+      }, py::arg("buffer"), py::arg("k"), py::arg("m"), py::arg("shard_len"), py::arg("stride"))
+      // rows x the resident blocks `block_ids` (each shard_len bytes) -> the rebuilt shards
+      .def("ec_decode", [](ChunkStore& s, std::vector<std::vector<int>> rows, std::vector<std::string> block_ids,
+                           uint64_t shard_len) -> py::object {
+        gf::Matrix M = to_matrix(rows);
+        std::vector<const uint8_t*> in;
+        ChunkStore::EcBuffers dec;
+        std::string err;
+        bool ok = true;
+        {
+          py::gil_scoped_release rel;
+          for (auto& id : block_ids) {
+            uint64_t size = 0;
+            const uint8_t* p = s.pin_device(id, &size);
+            if (p && size != shard_len) s.unpin(id);
+            if (!p || size != shard_len) {
+              ok = false;
+              break;
+            }
+            in.push_back(p);
+          }
+          if (ok) ok = s.ec_decode(M, in, shard_len, &dec, &err);
+          for (size_t i = 0; i < in.size(); ++i) s.unpin(block_ids[i]);
+        }
+        if (in.size() != block_ids.size()) throw std::runtime_error("ec_decode: a block is not resident at shard_len bytes");
+        if (!ok) return py::none();
+        return ec_result(s, &dec);
+      }, py::arg("rows"), py::arg("block_ids"), py::arg("shard_len"));
 
   // ---------------- native chunkserver control loop (csrc/cs_agent.cpp)
   py::class_<CsAgent>(m, "CsAgent")

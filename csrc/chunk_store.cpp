@@ -2554,6 +2554,8 @@ StoreStats ChunkStore::stats() {
   s.direct_dma = direct_dma_.load();
   s.fused_reads = fused_reads_.load();
   s.fused_writes = fused_writes_.load();
+  s.ec_fused_encodes = ec_fused_encodes_.load();
+  s.ec_fused_decodes = ec_fused_decodes_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -3674,7 +3676,50 @@ std::vector<std::string> ChunkStore::scrub_durable_gpu(const std::vector<std::st
 // ---------------------------------------------------------------- device erasure coding
 namespace {
 uint64_t ec_meta_stride(uint64_t len) { return align_up(std::max<uint64_t>(num_slices(len) * 4, 4), 256); }
+// Pinned-scratch layout of a fused stripe (ec_fused_kernel writes and reads it through the
+// device view): kMaxGridCrc partial words per shard, one tail word per shard, the GF tables.
+uint64_t ec_fused_tail_off(int nsh) { return static_cast<uint64_t>(nsh) * kMaxGridCrc * sizeof(uint32_t); }
+uint64_t ec_fused_table_off(int nsh) { return ec_fused_tail_off(nsh) + kMaxShards * sizeof(uint32_t); }
+bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 }  // namespace
+
+bool ChunkStore::ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
+                          std::vector<uint32_t>* crc, std::string* err) {
+  const int nsh = (a.encode ? a.k : 0) + a.rows;
+  const CrcPlan p = plan_crc(nullptr, len, nullptr, nullptr, true, 0, len);
+  a.s_full = p.a.s_full;
+  a.vfront = p.a.vfront;
+  a.ntiles = p.a.ntiles;
+  a.full_init = p.a.full_init;
+  a.tail_len = p.a.tail_len;
+  a.tail_init = p.a.tail_init;
+  std::vector<uint8_t> flat(static_cast<size_t>(a.rows) * a.k);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.k; ++c) flat[r * a.k + c] = mat[r][c];
+  gf_nibble_tables(flat.data(), a.rows, a.k, reinterpret_cast<uint32_t*>(l->hscratch + ec_fused_table_off(nsh)));
+  auto* hdev = static_cast<uint8_t*>(l->hscratch_dev);
+  a.part_crc = reinterpret_cast<uint32_t*>(hdev);
+  a.tail_be = reinterpret_cast<uint32_t*>(hdev + ec_fused_tail_off(nsh));
+  a.tables = reinterpret_cast<const uint32_t*>(hdev + ec_fused_table_off(nsh));
+  const int grid = ec_fused_grid(a.ntiles, a.tail_len, a.rows);
+  const hipError_t e = launch_ec_fused(a, dtables_, grid, l->stream);
+  launches_++;
+  if (e != hipSuccess) {
+    *err = std::string("fused EC kernel launch: ") + hipGetErrorString(e);
+    return false;
+  }
+  HIP_OK(hipStreamSynchronize(l->stream));
+  const auto* hp = reinterpret_cast<const uint32_t*>(l->hscratch);
+  const auto* tails = reinterpret_cast<const uint32_t*>(l->hscratch + ec_fused_tail_off(nsh));
+  crc->assign(nsh, 0);
+  for (int s = 0; s < nsh; ++s) {  // as write_copy() combines one block
+    uint32_t r = 0;
+    for (int g = 0; g < grid; ++g) r ^= hp[s * kMaxGridCrc + g];
+    if (a.tail_len) r = crc_shift(r, a.tail_len) ^ (__builtin_bswap32(tails[s]) ^ a.tail_init);
+    (*crc)[s] = r ^ crc_init_term(len);
+  }
+  return true;
+}
 
 bool ChunkStore::ec_encode(const uint8_t* host, uint64_t host_stride, uint64_t len, int k,
                            const std::vector<std::vector<uint8_t>>& parity, EcBuffers* out, std::string* err) {
@@ -3695,29 +3740,52 @@ bool ChunkStore::ec_encode(const uint8_t* host, uint64_t host_stride, uint64_t l
   uint8_t* metas = ext.ptr + stride * total;
   auto* dtab = reinterpret_cast<uint32_t*>(metas + ms * total);
   Lane* l = acquire_lane();
-  ensure_hscratch(l, tbytes + 16);
-  std::vector<uint8_t> flat(static_cast<size_t>(m) * k);
-  for (int r = 0; r < m; ++r)
-    for (int c = 0; c < k; ++c) flat[r * k + c] = parity[r][c];
-  auto* htab = reinterpret_cast<uint32_t*>(l->hscratch + 2 * kMaxGridCrc * sizeof(uint32_t) + 16);
-  gf_nibble_tables(flat.data(), m, k, htab);
-  HIP_OK(hipMemcpyAsync(dtab, htab, tbytes, hipMemcpyHostToDevice, l->stream));
-  for (int c = 0; c < k; ++c) h2d_chunked(l, ext.ptr + c * stride, host + c * host_stride, len);
-  GfLaunch a{};
-  a.k = k;
-  a.rows = m;
-  a.len = len;
-  a.tables = dtab;
-  for (int c = 0; c < k; ++c) a.in[c] = ext.ptr + c * stride;
-  for (int r = 0; r < m; ++r) a.out[r] = ext.ptr + (k + r) * stride;
-  bool ok = launch_gf_matmul(a, l->stream) == hipSuccess;
-  launches_++;
-  out->crc.assign(total, 0);
-  for (int i = 0; ok && i < total; ++i) {
-    CrcOut co;
-    ok = run_crc(l, ext.ptr + i * stride, len, reinterpret_cast<uint32_t*>(metas + i * ms), nullptr, true, 0, len,
-                 &co, err);
-    out->crc[i] = co.block_crc;
+  // The writer's stripe sits in registered memory: one kernel lands the k shards, computes the
+  // parity and checksums all k + m from registers (ec_fused_kernel). Otherwise the staged path:
+  // copies, K4, then one K2 launch and stream sync per shard.
+  const uint8_t* src_dev = nullptr;
+  if (m <= kEcFusedMaxRows && total <= kMaxShards && ec_fused_enabled() && crc_mfma_enabled() && aligned16(host) &&
+      host_stride % 16 == 0)
+    src_dev = device_view(host, host_stride * (k - 1) + len);
+  ensure_hscratch(l, src_dev ? ec_fused_table_off(total) + tbytes : tbytes + 16);
+  bool ok;
+  if (src_dev && l->hscratch_dev) {
+    EcFusedLaunch a{};
+    a.k = k;
+    a.rows = m;
+    a.encode = true;
+    for (int c = 0; c < k; ++c) {
+      a.in[c] = src_dev + c * host_stride;
+      a.dst[c] = ext.ptr + c * stride;
+    }
+    for (int r = 0; r < m; ++r) a.out[r] = ext.ptr + (k + r) * stride;
+    for (int i = 0; i < total; ++i) a.meta[i] = reinterpret_cast<uint32_t*>(metas + i * ms);
+    ok = ec_fused(l, a, parity, len, &out->crc, err);
+    if (ok) ec_fused_encodes_++;
+  } else {
+    std::vector<uint8_t> flat(static_cast<size_t>(m) * k);
+    for (int r = 0; r < m; ++r)
+      for (int c = 0; c < k; ++c) flat[r * k + c] = parity[r][c];
+    auto* htab = reinterpret_cast<uint32_t*>(l->hscratch + 2 * kMaxGridCrc * sizeof(uint32_t) + 16);
+    gf_nibble_tables(flat.data(), m, k, htab);
+    HIP_OK(hipMemcpyAsync(dtab, htab, tbytes, hipMemcpyHostToDevice, l->stream));
+    for (int c = 0; c < k; ++c) h2d_chunked(l, ext.ptr + c * stride, host + c * host_stride, len);
+    GfLaunch a{};
+    a.k = k;
+    a.rows = m;
+    a.len = len;
+    a.tables = dtab;
+    for (int c = 0; c < k; ++c) a.in[c] = ext.ptr + c * stride;
+    for (int r = 0; r < m; ++r) a.out[r] = ext.ptr + (k + r) * stride;
+    ok = launch_gf_matmul(a, l->stream) == hipSuccess;
+    launches_++;
+    out->crc.assign(total, 0);
+    for (int i = 0; ok && i < total; ++i) {
+      CrcOut co;
+      ok = run_crc(l, ext.ptr + i * stride, len, reinterpret_cast<uint32_t*>(metas + i * ms), nullptr, true, 0, len,
+                   &co, err);
+      out->crc[i] = co.block_crc;
+    }
   }
   if (ok) {
     HIP_OK(hipEventCreateWithFlags(&out->done, hipEventDisableTiming));
@@ -3733,6 +3801,7 @@ bool ChunkStore::ec_encode(const uint8_t* host, uint64_t host_stride, uint64_t l
   out->ext = ext;
   out->len = len;
   out->stride = stride;
+  out->meta_stride = ms;
   out->count = total;
   return true;
 }
@@ -3756,28 +3825,47 @@ bool ChunkStore::ec_decode(const std::vector<std::vector<uint8_t>>& rows, const 
   uint8_t* metas = ext.ptr + stride * nr;
   auto* dtab = reinterpret_cast<uint32_t*>(metas + ms * nr);
   Lane* l = acquire_lane();
-  ensure_hscratch(l, tbytes + 16);
-  std::vector<uint8_t> flat(static_cast<size_t>(nr) * k);
-  for (int r = 0; r < nr; ++r)
-    for (int c = 0; c < k; ++c) flat[r * k + c] = rows[r][c];
-  auto* htab = reinterpret_cast<uint32_t*>(l->hscratch + 2 * kMaxGridCrc * sizeof(uint32_t) + 16);
-  gf_nibble_tables(flat.data(), nr, k, htab);
-  HIP_OK(hipMemcpyAsync(dtab, htab, tbytes, hipMemcpyHostToDevice, l->stream));
-  GfLaunch a{};
-  a.k = k;
-  a.rows = nr;
-  a.len = len;
-  a.tables = dtab;
-  for (int c = 0; c < k; ++c) a.in[c] = in[c];
-  for (int r = 0; r < nr; ++r) a.out[r] = ext.ptr + r * stride;
-  bool ok = launch_gf_matmul(a, l->stream) == hipSuccess;
-  launches_++;
-  out->crc.assign(nr, 0);
-  for (int i = 0; ok && i < nr; ++i) {
-    CrcOut co;
-    ok = run_crc(l, ext.ptr + i * stride, len, reinterpret_cast<uint32_t*>(metas + i * ms), nullptr, true, 0, len,
-                 &co, err);
-    out->crc[i] = co.block_crc;
+  // reconstruct mode of ec_fused_kernel: the survivors are verified HBM shards, the rebuilt
+  // ones are checksummed from the registers they were computed in
+  bool fused = nr <= kEcFusedMaxRows && ec_fused_enabled() && crc_mfma_enabled();
+  for (int c = 0; c < k; ++c) fused = fused && aligned16(in[c]);
+  ensure_hscratch(l, fused ? ec_fused_table_off(nr) + tbytes : tbytes + 16);
+  bool ok;
+  if (fused && l->hscratch_dev) {
+    EcFusedLaunch a{};
+    a.k = k;
+    a.rows = nr;
+    a.encode = false;
+    for (int c = 0; c < k; ++c) a.in[c] = in[c];
+    for (int r = 0; r < nr; ++r) {
+      a.out[r] = ext.ptr + r * stride;
+      a.meta[r] = reinterpret_cast<uint32_t*>(metas + r * ms);
+    }
+    ok = ec_fused(l, a, rows, len, &out->crc, err);
+    if (ok) ec_fused_decodes_++;
+  } else {
+    std::vector<uint8_t> flat(static_cast<size_t>(nr) * k);
+    for (int r = 0; r < nr; ++r)
+      for (int c = 0; c < k; ++c) flat[r * k + c] = rows[r][c];
+    auto* htab = reinterpret_cast<uint32_t*>(l->hscratch + 2 * kMaxGridCrc * sizeof(uint32_t) + 16);
+    gf_nibble_tables(flat.data(), nr, k, htab);
+    HIP_OK(hipMemcpyAsync(dtab, htab, tbytes, hipMemcpyHostToDevice, l->stream));
+    GfLaunch a{};
+    a.k = k;
+    a.rows = nr;
+    a.len = len;
+    a.tables = dtab;
+    for (int c = 0; c < k; ++c) a.in[c] = in[c];
+    for (int r = 0; r < nr; ++r) a.out[r] = ext.ptr + r * stride;
+    ok = launch_gf_matmul(a, l->stream) == hipSuccess;
+    launches_++;
+    out->crc.assign(nr, 0);
+    for (int i = 0; ok && i < nr; ++i) {
+      CrcOut co;
+      ok = run_crc(l, ext.ptr + i * stride, len, reinterpret_cast<uint32_t*>(metas + i * ms), nullptr, true, 0, len,
+                   &co, err);
+      out->crc[i] = co.block_crc;
+    }
   }
   if (ok) {
     HIP_OK(hipEventCreateWithFlags(&out->done, hipEventDisableTiming));
@@ -3793,6 +3881,7 @@ bool ChunkStore::ec_decode(const std::vector<std::vector<uint8_t>>& rows, const 
   out->ext = ext;
   out->len = len;
   out->stride = stride;
+  out->meta_stride = ms;
   out->count = nr;
   return true;
 }

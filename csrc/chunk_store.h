@@ -91,6 +91,8 @@ struct StoreStats {
   uint64_t direct_dma = 0;       // host<->HBM copies done straight from registered memory
   uint64_t fused_reads = 0;      // reads delivered by the K3 verify+copy kernel (no SDMA copy)
   uint64_t fused_writes = 0;     // writes staged by the K1/K2 copy+checksum kernel (no SDMA copy)
+  uint64_t ec_fused_encodes = 0;  // RS stripes landed, encoded and checksummed by one ec_fused_kernel launch
+  uint64_t ec_fused_decodes = 0;  // shard sets rebuilt and checksummed by one ec_fused_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -273,11 +275,13 @@ class ChunkStore {
   // 1110-1165; chunkserver.rs:503-640 move every shard through host memory).
   struct EcBuffers {
     DevExtent ext;
-    uint64_t len = 0, stride = 0;
+    uint64_t len = 0, stride = 0, meta_stride = 0;
     int count = 0;
     std::vector<uint32_t> crc;   // whole-shard CRC-32 of each shard (K2)
     hipEvent_t done = nullptr;   // recorded after the kernels that produced the shards
     uint8_t* shard(int i) const { return ext.ptr + static_cast<uint64_t>(i) * stride; }
+    // HBM .meta image of shard i (BE CRC per 512 B slice), behind the shards
+    uint8_t* meta(int i) const { return ext.ptr + count * stride + static_cast<uint64_t>(i) * meta_stride; }
   };
   // k data stripes (host_stride apart in host memory; registered memory moves in one DMA
   // each) into HBM, the rows of `parity` x data computed next to them: out holds k + rows shards.
@@ -483,6 +487,11 @@ class ChunkStore {
   std::atomic<uint64_t> sliced_stages_{0};
   bool write_copy(Lane* l, const uint8_t* src_dev, uint8_t* dst, uint64_t n, uint32_t* dmeta, uint8_t* hmeta,
                   CrcOut* out, std::string* err);
+  // One ec_fused_kernel launch and stream sync for the stripe described by `a` (pointers, k, rows,
+  // encode set by the caller), then the per-shard combine of the whole-shard CRCs into `crc`.
+  bool ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
+                std::vector<uint32_t>* crc, std::string* err);
+  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

@@ -6,6 +6,8 @@
 //   K1b    crc_scrub_kernel: one launch verifies every resident block against its .meta.
 //   K4/K5  gf256_matmul_kernel: GF(2^8) matrix x shards (Reed-Solomon encode / reconstruct;
 //          reference erasure.rs:7-49).
+//   K4/K5 + K2  ec_fused_kernel: a whole RS stripe in one pass — the shards are landed (encode),
+//          multiplied and checksummed from the registers they were loaded or computed in.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -159,6 +161,34 @@ struct WriteCopyLaunch {
 bool crc_meta_host_ok(uint64_t ntiles);
 hipError_t launch_write_copy(const WriteCopyLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_gf_matmul(const GfLaunch& a, hipStream_t s);
+
+// K4/K5 fused with the shard checksums (ec_fused_kernel): one launch lands a whole RS stripe.
+// Encode: `in` are device views of the k data shards in registered host memory, `dst` their HBM
+// extents, `out` the `rows` parity shards; `meta` and the partials cover the k inputs, then the
+// outputs. Reconstruct: `in` are verified HBM shards, `dst` is unused, `meta` and the partials
+// cover the outputs only. Every pointer is 16 B aligned; shards are `len` bytes, and the plan
+// fields are those of a whole-block CrcLaunch of `len` bytes, shared by every shard.
+constexpr int kEcFusedMaxRows = 4;   // parity accumulators live in VGPRs
+constexpr int kEcFusedMaxGrid = 512;  // one resident round at 2 workgroups per CU
+struct EcFusedLaunch {
+  const uint8_t* in[kMaxShards];
+  uint8_t* dst[kMaxShards];
+  uint8_t* out[kEcFusedMaxRows];
+  uint32_t* meta[kMaxShards];  // HBM .meta image (BE CRC per slice) of each checksummed shard
+  uint64_t s_full, vfront, ntiles;
+  uint32_t full_init, tail_len, tail_init;
+  int k, rows;
+  bool encode;
+  const uint32_t* tables;  // device-visible: [rows][k] x 8 dwords (gf_nibble_tables)
+  uint32_t* part_crc;      // device-visible: [shard][kMaxGridCrc] raw shifted whole-shard partials
+  uint32_t* tail_be;       // device-visible: [shard] BE .meta word of the short tail slice
+};
+// DFS_EC_FUSED=0 keeps the staged path (copies, K4/K5, one K2 launch per shard); set_ec_fused is
+// the benches' A/B switch.
+bool ec_fused_enabled();
+void set_ec_fused(bool on);
+int ec_fused_grid(uint64_t ntiles, uint32_t tail_len, int rows);
+hipError_t launch_ec_fused(const EcFusedLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

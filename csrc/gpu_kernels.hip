@@ -1234,6 +1234,183 @@ __global__ __launch_bounds__(256) void gf256_matmul_kernel(GfLaunch a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// K4/K5 fused with K2: one pass over an RS stripe. The tile axis is the shard-relative 16 KiB
+// tile of a whole-block checksum plan (virtual front padding, balanced contiguous runs per
+// workgroup), and the same run is walked for every shard of the stripe. Per tile a wave loads
+// its 4 KiB of input c (encode: over PCIe from the writer's registered slot, prefetching the
+// next input or tile behind the current one's arithmetic), stores it into the shard's HBM
+// extent, checksums it on the matrix cores from the registers it sits in and multiplies it into
+// R parity accumulators that stay in VGPRs; after input k-1 the accumulators are stored and
+// checksummed the same way, so no shard byte is read twice and parity is never read at all.
+//  * Each wave keeps a running whole-shard partial per shard. Up to 32 of them are indexed by a
+//    loop variable, so they live in LDS (one word per wave and shard; the wave's own lanes are
+//    the only readers and writers inside the loop), not in a register array.
+//  * The GF split-nibble tables are read once per workgroup through the device view of the
+//    lane's pinned scratch into LDS (no table copy on the stream); the wave-uniform tables of
+//    one (row, input) pair are LDS broadcasts.
+//  * Short tail slice: byte-wise GF products keep the zero front padding of load_tail_wave, so
+//    the parity tail is the XOR of the products in that layout, checksummed like a data tail and
+//    stored byte-wise at the unpadded positions.
+//  * Reconstruct mode (kEncode = false): inputs are verified HBM shards — no input stores or
+//    checksums, only the R outputs.
+// Register budget: FP4 basis 32 VGPRs (the i8 form's 64 buy nothing here: encode is bound by
+// PCIe, reconstruct by the v_perm_b32 rate) + two WaveData 32 + R WaveData of parity + R x 8 table
+// dwords + the 16 MFMA accumulators + one 16 B group's 16 selector registers: ~200 at R = 4
+// before addresses and temporaries. That is over the 168 of 3 waves/SIMD for every R, so
+// R <= 3 runs at 2 waves/SIMD (256 registers, two workgroups per CU) and R = 4, which does not
+// fit 256 without scratch, at 1 wave/SIMD (one workgroup per CU; the overflow sits in AGPRs).
+// The next input's loads are in flight behind the arithmetic either way. LDS: 48 KiB image +
+// R KiB tables + 512 B partials. The compiler's report (-Rpass-analysis=kernel-resource-usage,
+// gfx950; VGPRs + AGPRs / LDS bytes / waves per SIMD; scratch is 0 in all eight):
+//   R  reconstruct             encode
+//   1  177      / 50688 / 2    199      / 50688 / 2
+//   2  196      / 51712 / 2    216      / 51712 / 2
+//   3  238      / 52736 / 2    252      / 52736 / 2
+//   4  256 + 62 / 53760 / 1    256 + 88 / 53760 / 1
+template <int R>
+__device__ __forceinline__ void gf_accumulate(const uint32_t* __restrict__ t, int k, int c, const WaveData& d,
+                                              WaveData (&pacc)[R]) {
+  uint32_t tb[R][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tb[r][j] = t[(r * k + c) * 8 + j];
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    // the selectors of an input dword are prepared once and reused for every row
+    const NibbleSel n0 = nibble_sel(d.v[v].x), n1 = nibble_sel(d.v[v].y), n2 = nibble_sel(d.v[v].z),
+                    n3 = nibble_sel(d.v[v].w);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      pacc[r].v[v].x ^= gf_mul4(tb[r], n0);
+      pacc[r].v[v].y ^= gf_mul4(tb[r], n1);
+      pacc[r].v[v].z ^= gf_mul4(tb[r], n2);
+      pacc[r].v[v].w ^= gf_mul4(tb[r], n3);
+    }
+    // one 16 B group at a time: interleaving the four groups keeps 64 selector registers live
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// Mirror of load_tail_wave: the bytes of the front-padded slice back to their unpadded places.
+__device__ __forceinline__ void store_tail_wave(uint8_t* __restrict__ base, uint32_t len, const WaveData& d, int lane) {
+  const int n = lane & 31, h = lane >> 5;
+  if (n >= 8) return;
+  const int pad = 512 - static_cast<int>(len);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const uint32_t w = seg_dword(d, 0, q);
+    for (int b = 0; b < 4; ++b) {
+      const int pos = n * 64 + h * 32 + q * 4 + b;
+      if (pos >= pad) base[pos - pad] = static_cast<uint8_t>(w >> (8 * b));
+    }
+  }
+}
+
+template <int R, bool kEncode>
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(R < 4 ? 2 : 1, R < 4 ? 2 : 1)))
+void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
+  static_assert(R >= 1 && R <= kEcFusedMaxRows, "parity accumulators in VGPRs");
+  __shared__ MfmaTileLds lt;
+  __shared__ uint32_t gft[R * kMaxShards * 8];
+  __shared__ uint32_t part[4][kMaxShards];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int k = a.k, first_out = kEncode ? k : 0, nsh = first_out + R;
+  const uint64_t t_begin = tile_run_begin(a.ntiles, blockIdx.x), t_end = tile_run_begin(a.ntiles, blockIdx.x + 1);
+  const int64_t hi = static_cast<int64_t>(a.s_full);
+  auto first_slice = [&](uint64_t t) {
+    return static_cast<int64_t>(t * kSlicesPerTile + wave * 8) - static_cast<int64_t>(a.vfront);
+  };
+  WaveData cur;
+  if (t_begin < t_end) cur = load_wave(a.in[0], first_slice(t_begin), 0, hi, lane);  // PCIe latency first
+  ChunkBasis<true> basis;
+  basis.load(gt, lane);
+  load_lds_image(gt, &lt);
+  for (int i = threadIdx.x; i < R * k * 8; i += kCrcWgThreads) gft[i] = a.tables[i];
+  if (threadIdx.x < 4 * kMaxShards) (&part[0][0])[threadIdx.x] = 0;
+  __syncthreads();
+
+  // slice CRCs of the wave's 4 KiB of shard s -> its .meta words and the wave's running partial
+  auto checksum = [&](int s, int64_t i0, const WaveData& d) {
+    uint32_t r = slice_from_chunks(lt, basis.crcs(d, lane), lane);
+    const int64_t i = i0 + sw;
+    if (i >= 0 && i < hi && sl == 0) a.meta[s][i] = __builtin_bswap32(r ^ a.full_init);
+    r = combine<8>(r, lane, lt.sh512);
+    r = combine<16>(r, lane, lt.sh1k);
+    r = combine<32>(r, lane, lt.sh2k);
+    const uint32_t acc = mat_apply(lt.tile_pow2[0], part[wave][s], lane) ^ r;
+    if (lane == 0) part[wave][s] = acc;
+  };
+
+  for (uint64_t t = t_begin; t < t_end; ++t) {
+    const int64_t i0 = first_slice(t);
+    WaveData pacc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) pacc[r].v[v] = make_uint4(0, 0, 0, 0);
+    for (int c = 0; c < k; ++c) {
+      const bool more = c + 1 < k || t + 1 < t_end;
+      WaveData nxt;
+      if (more) nxt = load_wave(a.in[c + 1 < k ? c + 1 : 0], c + 1 < k ? i0 : first_slice(t + 1), 0, hi, lane);
+      if constexpr (kEncode) {
+        store_wave_dst(a.dst[c], i0, 0, hi, cur, lane);
+        checksum(c, i0, cur);
+      }
+      gf_accumulate<R>(gft, k, c, cur, pacc);
+      if (more) cur = nxt;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      store_wave_dst(a.out[r], i0, 0, hi, pacc[r], lane);
+      checksum(first_out + r, i0, pacc[r]);
+    }
+  }
+
+  if (a.tail_len && blockIdx.x == 0 && wave == 0) {
+    const uint64_t off = a.s_full * 512;
+    auto tail = [&](int s, uint8_t* shard, const WaveData& d) {
+      const uint32_t r = slice_from_chunks(lt, basis.crcs(d, lane), lane);
+      if (lane == 0) {
+        const uint32_t be = __builtin_bswap32(r ^ a.tail_init);
+        a.meta[s][a.s_full] = be;
+        a.tail_be[s] = be;
+      }
+      store_tail_wave(shard + off, a.tail_len, d, lane);
+    };
+    WaveData pacc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) pacc[r].v[v] = make_uint4(0, 0, 0, 0);
+    for (int c = 0; c < k; ++c) {
+      const WaveData d = load_tail_wave(a.in[c] + off, a.tail_len, lane);
+      if constexpr (kEncode) tail(c, a.dst[c], d);
+      gf_accumulate<R>(gft, k, c, d, pacc);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) tail(first_out + r, a.out[r], pacc[r]);
+  }
+
+  // place the partials in the shard: (3 - wave) sub-tiles of the wave's last tile follow its
+  // accumulator (lane s shifts shard s), then — the shifts are linear, so once for the XOR of
+  // the four waves — the (ntiles - t_end) whole tiles behind the workgroup's run
+  if (lane < nsh) {
+    uint32_t v = part[wave][lane];
+    for (int j = wave; j < 3; ++j) v = tab4(lt.sh4k, v);
+    part[wave][lane] = v;
+  }
+  __syncthreads();
+  for (int s = wave; s < nsh; s += 4) {
+    uint32_t v = part[0][s] ^ part[1][s] ^ part[2][s] ^ part[3][s];
+    uint64_t e = t_begin < t_end ? a.ntiles - t_end : 0;
+    for (int b = 0; e; ++b, e >>= 1)
+      if (e & 1) v = mat_apply(lt.tile_pow2[b], v, lane);
+    if (lane == 0) a.part_crc[s * kMaxGridCrc + blockIdx.x] = v;
+  }
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -1537,6 +1714,62 @@ hipError_t launch_gf_matmul(const GfLaunch& a, hipStream_t s) {
   uint64_t blocks = (nvec + 255) / 256;
   int grid = static_cast<int>(blocks < 2048 ? blocks : 2048);
   hipLaunchKernelGGL(gf256_matmul_kernel, dim3(grid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_ec_fused{-1};
+
+void set_ec_fused(bool on) { g_ec_fused.store(on ? 1 : 0); }
+
+bool ec_fused_enabled() {
+  int v = g_ec_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_EC_FUSED");
+    g_ec_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+int ec_fused_grid(uint64_t ntiles, uint32_t tail_len, int rows) {
+  // one resident round: two workgroups per CU, one with four accumulator rows
+  const uint64_t cap = rows < 4 ? kEcFusedMaxGrid : kEcFusedMaxGrid / 2;
+  const uint64_t g = ntiles < cap ? ntiles : cap;
+  return static_cast<int>(g == 0 && tail_len ? 1 : g);
+}
+
+hipError_t launch_ec_fused(const EcFusedLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  if (grid <= 0) return hipSuccess;
+  static_assert(kEcFusedMaxGrid <= kMaxGridCrc, "part_crc holds kMaxGridCrc words per shard");
+  const int nsh = (a.encode ? a.k : 0) + a.rows;
+  if (grid > kMaxGridCrc || a.k <= 0 || a.k > kMaxShards || a.rows <= 0 || a.rows > kEcFusedMaxRows ||
+      nsh > kMaxShards || !a.tables || !a.part_crc || !a.tail_be)
+    return hipErrorInvalidValue;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(a.tables) | reinterpret_cast<uintptr_t>(a.part_crc) |
+                   reinterpret_cast<uintptr_t>(a.tail_be);
+  for (int c = 0; c < a.k; ++c) {
+    if (!a.in[c] || (a.encode && !a.dst[c])) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(a.in[c]) | (a.encode ? reinterpret_cast<uintptr_t>(a.dst[c]) : 0);
+  }
+  for (int r = 0; r < a.rows; ++r) {
+    if (!a.out[r]) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(a.out[r]);
+  }
+  for (int i = 0; i < nsh; ++i) {
+    if (!a.meta[i]) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(a.meta[i]);
+  }
+  if (bits % 16) return hipErrorInvalidValue;
+  const dim3 g(grid), b(kCrcWgThreads);
+  switch (a.rows * 2 + (a.encode ? 1 : 0)) {
+    case 2: hipLaunchKernelGGL((ec_fused_kernel<1, false>), g, b, 0, s, a, t); break;
+    case 3: hipLaunchKernelGGL((ec_fused_kernel<1, true>), g, b, 0, s, a, t); break;
+    case 4: hipLaunchKernelGGL((ec_fused_kernel<2, false>), g, b, 0, s, a, t); break;
+    case 5: hipLaunchKernelGGL((ec_fused_kernel<2, true>), g, b, 0, s, a, t); break;
+    case 6: hipLaunchKernelGGL((ec_fused_kernel<3, false>), g, b, 0, s, a, t); break;
+    case 7: hipLaunchKernelGGL((ec_fused_kernel<3, true>), g, b, 0, s, a, t); break;
+    case 8: hipLaunchKernelGGL((ec_fused_kernel<4, false>), g, b, 0, s, a, t); break;
+    default: hipLaunchKernelGGL((ec_fused_kernel<4, true>), g, b, 0, s, a, t); break;
+  }
   return hipGetLastError();
 }
 

@@ -573,8 +573,117 @@ static int ec_fused_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// --ec-read: ChunkStore::ec_read_range of a resident RS(6,3) file with 1 and 2 lost data columns
+// into a registered buffer: the whole file and a 64 KiB range inside the first lost column, the
+// single-kernel path against the staged one (ec_decode into HBM, then one copy per column),
+// alternating in every repetition. One JSON line per (shard length, lost, range) cell; times are
+// microseconds per read, each the mean of `iters` back-to-back reads.
+static int ec_read_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--ec-read needs a GPU\n");
+    return 1;
+  }
+  std::filesystem::remove_all(dir);
+  StoreConfig cfg;
+  cfg.storage_dir = dir + "/ecr";
+  cfg.device = device;
+  cfg.hbm_capacity = 2ull << 30;
+  ChunkStore s(cfg);
+  const int k = 6, m = 3;
+  int rc = 0;
+  for (uint64_t len : {256ull << 10, 1ull << 20, 16ull << 20}) {
+    const auto data = random_bytes(k * len, static_cast<uint32_t>(len + 17));
+    std::vector<std::vector<uint8_t>> par(m, std::vector<uint8_t>(len));
+    std::vector<const uint8_t*> in(k);
+    std::vector<uint8_t*> outp(m);
+    for (int c = 0; c < k; ++c) in[c] = data.data() + c * len;
+    for (int r = 0; r < m; ++r) outp[r] = par[r].data();
+    gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+    gf::matmul_cpu(parity, in.data(), outp.data(), len);
+    std::vector<std::string> ids;
+    std::vector<const uint8_t*> dev(k + m, nullptr);
+    bool ok = true;
+    for (int i = 0; i < k + m; ++i) {
+      const uint8_t* p = i < k ? in[i] : par[i - k].data();
+      ids.push_back("ecr_" + std::to_string(len) + "_" + std::to_string(i));
+      ok = ok && s.write(ids[i], p, len, crc32(p, len)).ok;
+      uint64_t size = 0;
+      if (ok) dev[i] = s.pin_device(ids[i], &size);
+      ok = ok && dev[i] && size == len;
+    }
+    uint8_t* buf = nullptr;
+    if (!ok || hipHostMalloc(reinterpret_cast<void**>(&buf), k * len, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
+      return 1;
+    s.register_host(buf, k * len);
+    for (int lost = 1; lost <= 2; ++lost)
+      for (int whole = 1; whole >= 0; --whole) {
+        std::vector<const uint8_t*> shards = dev;
+        for (int c = 0; c < lost; ++c) shards[2 * c + 1] = nullptr;  // columns 1 and 3
+        const uint64_t from = whole ? 0 : len + len / 2 + 5, want = whole ? k * len : 64ull << 10;
+        const int iters = static_cast<int>(std::clamp<uint64_t>((256ull << 20) / (whole ? k * len : len), 3, 100));
+        std::vector<double> us[2];  // [0] staged, [1] fused
+        bool match = true;
+        auto run = [&](int fused, int n) {
+          set_ec_read_fused(fused != 0);
+          std::memset(buf, 0, want);
+          const auto t0 = Clock::now();
+          for (int i = 0; i < n && match; ++i) {
+            std::string err;
+            match = s.ec_read_range(shards, k, m, len, from, want, buf, &err) == ChunkStore::EcRead::Ok;
+          }
+          const double t = secs(t0, Clock::now()) * 1e6 / n;
+          match = match && std::memcmp(buf, data.data() + from, want) == 0;
+          return t;
+        };
+        for (int fused = 0; fused < 2; ++fused) run(fused, 2);  // warm-up: code objects, scratch, extents
+        const uint64_t before = s.stats().ec_fused_reads;
+        for (int rep = 0; rep < reps; ++rep)
+          for (int fused = 1; fused >= 0; --fused) us[fused].push_back(run(fused, iters));
+        match = match && s.stats().ec_fused_reads - before == static_cast<uint64_t>(reps) * iters;
+        auto list = [](const std::vector<double>& v) {
+          std::string o;
+          for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+          return o;
+        };
+        auto median = [](std::vector<double> v) {
+          std::sort(v.begin(), v.end());
+          return v[v.size() / 2];
+        };
+        std::printf("{\"ec_read\": {\"k\": %d, \"m\": %d, \"shard_len\": %llu, \"lost\": %d, \"from\": %llu, \"want\": %llu, "
+                    "\"iters\": %d, \"fused_us\": [%s], \"staged_us\": [%s], \"fused_median_us\": %.1f, "
+                    "\"staged_median_us\": %.1f, \"match\": %s}}\n",
+                    k, m, static_cast<unsigned long long>(len), lost, static_cast<unsigned long long>(from),
+                    static_cast<unsigned long long>(want), iters, list(us[1]).c_str(), list(us[0]).c_str(), median(us[1]),
+                    median(us[0]), match ? "true" : "false");
+        std::fflush(stdout);
+        if (!match) rc = 1;
+      }
+    s.unregister_host(buf);
+    (void)hipHostFree(buf);
+    for (auto& id : ids) {
+      s.unpin(id);
+      s.remove(id);
+    }
+  }
+  set_ec_read_fused(true);
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 int main(int argc, char** argv) {
   dfs::trace_init();  // before any thread: roctx's first range calls setenv (trace.h)
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--ec-read") {
+      std::string dir = "/tmp/io_bench_ecr";
+      int device = 0, reps = 5;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return ec_read_bench(device, dir, std::max(1, reps));
+    }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--ec-fused") {
       std::string dir = "/tmp/io_bench_ecf";

@@ -244,6 +244,7 @@ PYBIND11_MODULE(_dfs_native, m) {
   m.def("crc_fp4_enabled", &crc_fp4_enabled);
   m.def("set_crc_fp4", &set_crc_fp4, "wide K1/K2: chunk CRCs on the FP4 matrix cores (else i8)");
   m.def("set_ec_fused", &set_ec_fused, "device EC in one fused kernel per stripe (else copies, K4/K5, K2 per shard)");
+  m.def("set_ec_read_fused", &set_ec_read_fused, "degraded EC range reads in one kernel (else decode into HBM, then copies)");
   m.def("set_crc_wide", &set_crc_wide, "K1/K2 one workgroup per CU: 0 off, 1 shared LDS image, 2 + LDS basis");
   m.def("set_crc_kernels", [](bool mfma, int scrub_ring, int tile_ring) {
     set_crc_mfma(mfma);
@@ -502,7 +503,44 @@ PYBIND11_MODULE(_dfs_native, m) {
         if (in.size() != block_ids.size()) throw std::runtime_error("ec_decode: a block is not resident at shard_len bytes");
         if (!ok) return py::none();
         return ec_result(s, &dec);
-      }, py::arg("rows"), py::arg("block_ids"), py::arg("shard_len"));
+      }, py::arg("rows"), py::arg("block_ids"), py::arg("shard_len"))
+      // degraded read: bytes [offset, offset + length) of the RS(k, m) file whose k + m shards are
+      // the resident blocks `block_ids` ("" = lost) into `out`; a registered `out` takes the
+      // single-kernel path. Returns the number of bytes placed, None on failure.
+      .def("ec_read", [](ChunkStore& s, std::vector<std::string> block_ids, int k, int m, uint64_t shard_len,
+                         uint64_t offset, uint64_t length, py::buffer out) -> py::object {
+        py::buffer_info bi = out.request(true);
+        if (k <= 0 || m < 0 || block_ids.size() != static_cast<size_t>(k + m) || shard_len == 0 ||
+            offset >= shard_len * k)
+          throw std::invalid_argument("ec_read: k + m block ids and an offset inside the k shards");
+        const uint64_t want = std::min<uint64_t>(length, shard_len * k - offset);
+        if (want == 0 || want > static_cast<uint64_t>(bi.size * bi.itemsize))
+          throw std::invalid_argument("ec_read: empty range or destination too small");
+        std::vector<const uint8_t*> shards(block_ids.size(), nullptr);
+        std::string err;
+        bool resident = true;
+        ChunkStore::EcRead r = ChunkStore::EcRead::DecodeFailed;
+        {
+          py::gil_scoped_release rel;
+          for (size_t i = 0; i < block_ids.size() && resident; ++i) {
+            if (block_ids[i].empty()) continue;
+            uint64_t size = 0;
+            shards[i] = s.pin_device(block_ids[i], &size);
+            if (shards[i] && size != shard_len) {
+              s.unpin(block_ids[i]);
+              shards[i] = nullptr;
+            }
+            resident = shards[i] != nullptr;
+          }
+          if (resident) r = s.ec_read_range(shards, k, m, shard_len, offset, want, static_cast<uint8_t*>(bi.ptr), &err);
+          for (size_t i = 0; i < block_ids.size(); ++i)
+            if (shards[i]) s.unpin(block_ids[i]);
+        }
+        if (!resident) throw std::runtime_error("ec_read: a block is not resident at shard_len bytes");
+        if (r != ChunkStore::EcRead::Ok) return py::none();
+        return py::cast(want);
+      }, py::arg("block_ids"), py::arg("k"), py::arg("m"), py::arg("shard_len"), py::arg("offset"), py::arg("length"),
+         py::arg("out"));
 
   // ---------------- native chunkserver control loop (csrc/cs_agent.cpp)
   py::class_<CsAgent>(m, "CsAgent")

@@ -2556,6 +2556,7 @@ StoreStats ChunkStore::stats() {
   s.fused_writes = fused_writes_.load();
   s.ec_fused_encodes = ec_fused_encodes_.load();
   s.ec_fused_decodes = ec_fused_decodes_.load();
+  s.ec_fused_reads = ec_fused_reads_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -3894,6 +3895,86 @@ void ChunkStore::ec_free(EcBuffers* b) {
   if (b->ext.off >= 0) release(b->ext);
   b->ext = DevExtent{};
   b->count = 0;
+}
+
+ChunkStore::EcRead ChunkStore::ec_read_range(const std::vector<const uint8_t*>& shards, int k, int m, uint64_t sl,
+                                             uint64_t from, uint64_t want, uint8_t* dst, std::string* err) {
+  TraceRange tr("dfs.store.ec_read_range");
+  if (!gpu() || k <= 0 || m < 0 || k + m > kMaxShards || static_cast<int>(shards.size()) != k + m || sl == 0 ||
+      want == 0 || from + want > sl * k || !dst) {
+    *err = "device EC read needs a GPU store, 1..32 shards and a range inside them";
+    return EcRead::DecodeFailed;
+  }
+  std::vector<int> present, missing;  // missing: the lost data columns that the range touches
+  for (int i = 0; i < k + m && static_cast<int>(present.size()) < k; ++i)
+    if (shards[i]) present.push_back(i);
+  if (static_cast<int>(present.size()) < k) {
+    *err = "RS reconstruct error: TooFewShardsPresent";
+    return EcRead::DecodeFailed;
+  }
+  for (int c = 0; c < k; ++c)
+    if (!shards[c] && from < (c + 1) * sl && from + want > c * sl) missing.push_back(c);
+  const int nr = static_cast<int>(missing.size());
+  gf::Matrix rows;
+  if (nr) rows = gf::rs_decode_rows(k, m, present, missing);
+  std::vector<const uint8_t*> in;
+  for (int i : present) in.push_back(shards[i]);
+  HIP_OK(hipSetDevice(cfg_.device));
+
+  bool fused = ec_read_fused_enabled() && sl >= kEcReadMinShard && nr <= kEcFusedMaxRows && aligned16(dst);
+  for (int j = 0; j < k; ++j) fused = fused && aligned16(in[j]);
+  uint8_t* dst_dev = fused ? device_view(dst, want) : nullptr;
+  if (dst_dev) {
+    Lane* l = acquire_lane();
+    const uint64_t tbytes = static_cast<uint64_t>(nr) * k * 32;
+    ensure_hscratch(l, tbytes + 16);
+    if (nr == 0 || l->hscratch_dev) {
+      EcReadLaunch a{};
+      a.k = k;
+      a.rows = nr;
+      a.sl = sl;
+      a.from = from;
+      a.want = want;
+      a.out = dst_dev;
+      for (int j = 0; j < k; ++j) {
+        a.in[j] = in[j];
+        a.surv_col[j] = static_cast<int8_t>(present[j] < k ? present[j] : -1);
+      }
+      for (int r = 0; r < nr; ++r) a.row_col[r] = static_cast<int8_t>(missing[r]);
+      if (nr) {
+        std::vector<uint8_t> flat(static_cast<size_t>(nr) * k);
+        for (int r = 0; r < nr; ++r)
+          for (int c = 0; c < k; ++c) flat[r * k + c] = rows[r][c];
+        gf_nibble_tables(flat.data(), nr, k, reinterpret_cast<uint32_t*>(l->hscratch));
+        a.tables = static_cast<const uint32_t*>(l->hscratch_dev);
+      }
+      const hipError_t e = launch_ec_read(a, l->stream);
+      launches_++;
+      if (e == hipSuccess) HIP_OK(hipStreamSynchronize(l->stream));
+      release_lane(l);
+      if (e != hipSuccess) {
+        *err = std::string("EC read kernel launch: ") + hipGetErrorString(e);
+        return EcRead::DecodeFailed;
+      }
+      ec_fused_reads_++;
+      return EcRead::Ok;
+    }
+    release_lane(l);
+  }
+
+  EcBuffers dec;
+  if (nr && !ec_decode(rows, in, sl, &dec, err)) return EcRead::DecodeFailed;
+  // the requested range of the original bytes, column by column, HBM -> host
+  bool ok = true;
+  for (int c = 0; ok && c < k; ++c) {
+    const uint64_t lo = std::max<uint64_t>(from, c * sl), hi = std::min<uint64_t>(from + want, (c + 1) * sl);
+    if (lo >= hi) continue;
+    const uint8_t* src = shards[c];
+    if (!src) src = dec.shard(static_cast<int>(std::find(missing.begin(), missing.end(), c) - missing.begin()));
+    ok = device_to_host(dst + (lo - from), src + (lo - c * sl), hi - lo);
+  }
+  ec_free(&dec);
+  return ok ? EcRead::Ok : EcRead::CopyFailed;
 }
 
 bool ChunkStore::device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n) {

@@ -93,6 +93,7 @@ struct StoreStats {
   uint64_t fused_writes = 0;     // writes staged by the K1/K2 copy+checksum kernel (no SDMA copy)
   uint64_t ec_fused_encodes = 0;  // RS stripes landed, encoded and checksummed by one ec_fused_kernel launch
   uint64_t ec_fused_decodes = 0;  // shard sets rebuilt and checksummed by one ec_fused_kernel launch
+  uint64_t ec_fused_reads = 0;    // degraded EC range reads served by one ec_read_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -291,6 +292,15 @@ class ChunkStore {
   bool ec_decode(const std::vector<std::vector<uint8_t>>& rows, const std::vector<const uint8_t*>& in, uint64_t len,
                  EcBuffers* out, std::string* err);
   void ec_free(EcBuffers* b);
+  // Bytes [from, from + want) of an RS(k, m) file (0 < want, from + want <= k * sl) into host
+  // memory `dst`. `shards` are the k + m device pointers of sl bytes each, nullptr = lost; the
+  // first k present ones are used and only the lost data columns inside the range are rebuilt.
+  // Registered 16 B aligned `dst`, sl >= kEcReadMinShard and at most kEcFusedMaxRows columns to
+  // rebuild: one ec_read_kernel launch that stores the range from registers. Otherwise staged:
+  // ec_decode of those columns into HBM, then one copy per column.
+  enum class EcRead { Ok, DecodeFailed, CopyFailed };
+  EcRead ec_read_range(const std::vector<const uint8_t*>& shards, int k, int m, uint64_t sl, uint64_t from,
+                       uint64_t want, uint8_t* dst, std::string* err);
   // Device bytes into host memory (registered: one DMA) and synchronously complete.
   bool device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n);
   // A copy of device bytes committed as block `id` (checksummed, verified, made durable).
@@ -491,7 +501,7 @@ class ChunkStore {
   // encode set by the caller), then the per-shard combine of the whole-shard CRCs into `crc`.
   bool ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
                 std::vector<uint32_t>* crc, std::string* err);
-  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0};
+  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

@@ -38,6 +38,7 @@ Json stats_json(const StoreStats& t) {
   d.set("fused_writes", t.fused_writes);
   d.set("ec_fused_encodes", t.ec_fused_encodes);
   d.set("ec_fused_decodes", t.ec_fused_decodes);
+  d.set("ec_fused_reads", t.ec_fused_reads);
   d.set("pulled_recvs", t.pulled_recvs);
   d.set("pulled_host_appends", t.pulled_host_appends);
   d.set("sliced_stages", t.sliced_stages);

@@ -1235,39 +1235,24 @@ bool FastPathServer::ec_read(int fd, const uint8_t* body, const uint8_t* end) {
   if (base == nullptr) return fallback(want > cap ? "slot too small" : "short-circuit unavailable: " + err);
   EcGather g;
   if (!ec_gather(id, locs, sl, -1, k, &g, &err)) return fallback(err);
-  std::vector<int> present, missing;
+  int present = 0, missing = 0;
   for (int i = 0; i < k + m; ++i)
-    if (g.ptrs[i]) present.push_back(i);
-    else if (i < k) missing.push_back(i);
-  if (static_cast<int>(present.size()) < k) {
+    if (g.ptrs[i]) present++;
+    else if (i < k) missing++;
+  if (present < k) {
     if (g.unreachable > 0) return fallback("surviving shards not reachable over the engine");
     return send_response(fd, FpStatus::IoError, 0, 0, "RS reconstruct error: TooFewShardsPresent");
   }
-  present.resize(k);
-  ChunkStore::EcBuffers dec;
-  if (!missing.empty()) {
-    std::vector<const uint8_t*> in;
-    for (int i : present) in.push_back(g.ptrs[i]);
-    gf::Matrix rows = gf::rs_decode_rows(k, m, present, missing);
-    if (!store_->ec_decode(rows, in, sl, &dec, &err)) return fallback(err);
-  }
-  // the requested range of the original bytes, stripe by stripe, HBM -> the client's slot
-  bool ok = true;
-  for (int c = 0; ok && c < k; ++c) {
-    const uint64_t lo = std::max<uint64_t>(from, c * sl), hi = std::min<uint64_t>(from + want, (c + 1) * sl);
-    if (lo >= hi) continue;
-    const uint8_t* src = g.ptrs[c];
-    if (!src) {
-      auto it = std::find(missing.begin(), missing.end(), c);
-      src = dec.shard(static_cast<int>(it - missing.begin()));
-    }
-    ok = store_->device_to_host(base + shm_off + (lo - from), src + (lo - c * sl), hi - lo);
-  }
-  store_->ec_free(&dec);
+  // the requested range of the original bytes into the client's slot: one kernel where the slot
+  // is registered, else decode into HBM and copy column by column
+  const std::vector<const uint8_t*> shards(g.ptrs.begin(), g.ptrs.begin() + k + m);
+  const ChunkStore::EcRead r = store_->ec_read_range(shards, k, m, sl, from, want, base + shm_off, &err);
+  if (r == ChunkStore::EcRead::DecodeFailed) return fallback(err);
+  const bool ok = r == ChunkStore::EcRead::Ok;
   {
     std::lock_guard<std::mutex> lk(mu_);
     st_.ec_device_reads++;
-    if (!missing.empty()) st_.ec_device_decodes++;
+    if (missing > 0) st_.ec_device_decodes++;
   }
   return ok ? send_response(fd, FpStatus::Ok, orig, want, "") : send_response(fd, FpStatus::IoError, 0, 0, "copy out failed");
 }

@@ -8,6 +8,9 @@
 //          reference erasure.rs:7-49).
 //   K4/K5 + K2  ec_fused_kernel: a whole RS stripe in one pass — the shards are landed (encode),
 //          multiplied and checksummed from the registers they were loaded or computed in.
+//   K5 + range read  ec_read_kernel: a byte range of an RS-coded file whose data shards are partly
+//          lost — only the lost columns inside the range are rebuilt, and the bytes go from the
+//          registers over PCIe into the reader's registered buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -189,6 +192,34 @@ bool ec_fused_enabled();
 void set_ec_fused(bool on);
 int ec_fused_grid(uint64_t ntiles, uint32_t tail_len, int rows);
 hipError_t launch_ec_fused(const EcFusedLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// Degraded range read of an RS(k, m) file (ec_read_kernel): bytes [from, from + want) of the
+// original file — byte x is byte x % sl of data column x / sl — into `out`, the 16 B aligned
+// device view of registered host memory, which receives exactly `want` bytes. `in` are any k
+// surviving shards in HBM (16 B aligned, sl bytes in buffers padded to 16 B). A data column is
+// either a survivor (surv_col[j] = c, copied with the byte shift between its place in the shard
+// and its place in `out`) or, where it is lost and inside the range, the product of reconstruct
+// row r with the survivors (row_col[r] = c; tables as gf_nibble_tables lays out [rows][k]).
+// Lost columns outside the range are neither named nor computed. Limits: sl >= kEcReadMinShard,
+// rows <= kEcFusedMaxRows, 0 < want, from + want <= k * sl.
+constexpr uint64_t kEcReadMinShard = 1024;  // one wave step: 64 lanes x 16 B
+constexpr int kEcReadMaxGrid = 1024;        // one resident round at 4 workgroups per CU
+struct EcReadLaunch {
+  const uint8_t* in[kMaxShards];
+  int8_t surv_col[kMaxShards];       // data column that survivor j is, -1 for a parity shard
+  int8_t row_col[kEcFusedMaxRows];   // data column that reconstruct row r rebuilds
+  int k, rows;
+  uint64_t sl, from, want;
+  const uint32_t* tables;  // device-visible: [rows][k] x 8 dwords; unused when rows == 0
+  uint8_t* out;
+  // set by launch_ec_read: the (at most two) runs of wave steps that some column needs
+  uint64_t seg_begin[2], seg_steps[2];
+};
+// DFS_EC_READ_FUSED=0 keeps the staged degraded read (ec_decode of whole shards into HBM, then one
+// copy per column); set_ec_read_fused is the benches' A/B switch.
+bool ec_read_fused_enabled();
+void set_ec_read_fused(bool on);
+hipError_t launch_ec_read(const EcReadLaunch& a, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

@@ -1411,6 +1411,219 @@ void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// K5 for a degraded range read: bytes [from, from + want) of an RS-coded file go from the
+// surviving shards in HBM straight into the reader's registered buffer. The kernel walks the
+// SOURCE axis: every shard shares the shard-relative position p, data column c wants the
+// positions [lo_c, hi_c) that the range cuts out of it, and a wave step is the 64 aligned 16 B
+// vectors (1 KiB) at p = 1024 * step. Which columns want a step is wave-uniform (scalar
+// compares); the steps that some column wants form at most two runs (launch_ec_read), and each
+// wave takes a balanced contiguous piece of them, as tile_run_begin splits tiles.
+//  * Loads. At a step survivor j is loaded once if it is a data column that wants the step, or
+//    if any lost column wants it; the next survivor's load is issued before the current one's
+//    arithmetic. A copied column and the rebuild share the registers of that one load.
+//  * Arithmetic. The vector is multiplied into the R accumulators with the split-nibble
+//    v_perm_b32 form of K4/K5 (selectors once per input dword, reused for every row); the
+//    tables come through the device view of the lane's pinned scratch into LDS once per
+//    workgroup and are LDS broadcasts after that.
+//  * Shift. Column c's byte at p lands at out + c * sl - from + p, so with p % 16 == 0 the
+//    source and destination vectors differ by the byte shift (c * sl - from) % 16: uniform per
+//    column, a scalar. Each lane builds ONE destination-aligned vector from its own source vector
+//    and its lower neighbour's (v_mov_b32_dpp wave_shr:1, then v_alignbyte_b32 by the scalar
+//    shift). Lane 0's neighbour is the previous step's lane 63: a copied column reloads that one
+//    vector; a rebuilt column carries it in scalar registers from the wave's previous step, or,
+//    at the start of a run, rebuilds that single vector (one broadcast load per survivor).
+//  * Stores. A destination vector that lies inside the column's window of `out` is one aligned
+//    16 B store, wave-contiguous; the at most two vectors per column that straddle the window's
+//    edges are stored byte-wise under the window test, so nothing outside [out, out + want) is
+//    written and the zero padding behind the file's end is never emitted.
+// No checksums (the survivors were verified where they were gathered, the bytes go to the
+// client), no HBM output, no matrix cores. The compiler's report
+// (-Rpass-analysis=kernel-resource-usage, gfx950; scratch is 0 in all five):
+//   R  VGPRs  SGPRs  LDS bytes  waves per SIMD
+//   0   40     82          0  8
+//   1   67     98       1024  7
+//   2   98    106       2048  4
+//   3  118    106       3072  4
+//   4  137    106       4096  3
+struct EcReadCol {
+  uint64_t lo, hi;  // shard-relative positions inside the range (lo == hi: none)
+  // wave steps that hold a source vector of the column's destination vectors: the vector behind
+  // the last byte supplies the lower neighbour of the last, shifted, destination vector
+  __host__ __device__ uint64_t first_step() const { return lo / 1024; }
+  __host__ __device__ uint64_t last_step() const { return ((hi - 1) / 16 + 1) / 64; }
+};
+
+__host__ __device__ inline EcReadCol ec_read_col(uint64_t sl, uint64_t from, uint64_t want, uint64_t c) {
+  const uint64_t b = c * sl, lo = from > b ? from : b, hi = from + want < b + sl ? from + want : b + sl;
+  return lo < hi ? EcReadCol{lo - b, hi - b} : EcReadCol{0, 0};
+}
+
+template <int R>
+__device__ __forceinline__ void gf_accumulate16(const uint32_t* __restrict__ t, int k, int j, const uint4& d,
+                                                uint4 (&acc)[R]) {
+  uint32_t tb[R][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) tb[r][q] = t[(r * k + j) * 8 + q];
+  const NibbleSel n0 = nibble_sel(d.x), n1 = nibble_sel(d.y), n2 = nibble_sel(d.z), n3 = nibble_sel(d.w);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    acc[r].x ^= gf_mul4(tb[r], n0);
+    acc[r].y ^= gf_mul4(tb[r], n1);
+    acc[r].z ^= gf_mul4(tb[r], n2);
+    acc[r].w ^= gf_mul4(tb[r], n3);
+  }
+}
+
+// Lane L takes lane L - 1's x; lane 0, which has no lower neighbour, keeps `first`.
+__device__ __forceinline__ uint32_t lane_below(uint32_t x, uint32_t first) {
+  return static_cast<uint32_t>(
+      __builtin_amdgcn_update_dpp(static_cast<int>(first), static_cast<int>(x), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+}
+
+// One column's share of a wave step: `cur` is the lane's source vector v of the column, `first`
+// the vector v0 - 1 below lane 0's. Destination vector q = v + floor(delta / 16) takes its low
+// `shift` bytes from the top of vector v - 1 and the rest from the bottom of vector v.
+__device__ __forceinline__ void shift_store(uint8_t* __restrict__ out, int64_t delta, int64_t dlo, int64_t dhi, int64_t v,
+                                            const uint4& cur, const uint4& first) {
+  const uint32_t shift = static_cast<uint32_t>(delta) & 15u;
+  uint4 val = cur;
+  if (shift) {  // uniform
+    const uint4 prev = make_uint4(lane_below(cur.x, first.x), lane_below(cur.y, first.y), lane_below(cur.z, first.z),
+                                  lane_below(cur.w, first.w));
+    // bytes [16 - shift, 32 - shift) of prev:cur; dword w, byte b of it
+    const uint32_t w = (16u - shift) >> 2, b = (16u - shift) & 3u;
+    uint32_t e0, e1, e2, e3, e4;
+    switch (w) {
+      case 0: e0 = prev.x; e1 = prev.y; e2 = prev.z; e3 = prev.w; e4 = cur.x; break;
+      case 1: e0 = prev.y; e1 = prev.z; e2 = prev.w; e3 = cur.x; e4 = cur.y; break;
+      case 2: e0 = prev.z; e1 = prev.w; e2 = cur.x; e3 = cur.y; e4 = cur.z; break;
+      default: e0 = prev.w; e1 = cur.x; e2 = cur.y; e3 = cur.z; e4 = cur.w; break;
+    }
+    val = make_uint4(__builtin_amdgcn_alignbyte(e1, e0, b), __builtin_amdgcn_alignbyte(e2, e1, b),
+                     __builtin_amdgcn_alignbyte(e3, e2, b), __builtin_amdgcn_alignbyte(e4, e3, b));
+  }
+  const int64_t pos = ((delta >> 4) + v) * 16;  // of the destination vector in `out`
+  if (pos >= dlo && pos + 16 <= dhi) {
+    *reinterpret_cast<uint4*>(out + pos) = val;
+  } else if (pos + 16 > dlo && pos < dhi) {  // a window edge: at most two vectors per column
+    const uint32_t word[4] = {val.x, val.y, val.z, val.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (pos + i >= dlo && pos + i < dhi) out[pos + i] = static_cast<uint8_t>(word[i >> 2] >> (8 * (i & 3)));
+  }
+}
+
+template <int R>
+__global__ __launch_bounds__(kCrcWgThreads) void ec_read_kernel(EcReadLaunch a) {
+  static_assert(R >= 0 && R <= kEcFusedMaxRows, "accumulators in VGPRs");
+  constexpr int RR = R ? R : 1;
+  __shared__ uint32_t gft[RR * kMaxShards * 8];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), k = a.k;
+  if constexpr (R > 0) {
+    for (int i = threadIdx.x; i < R * k * 8; i += kCrcWgThreads) gft[i] = a.tables[i];
+    __syncthreads();
+  }
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const uint64_t sl = a.sl, from = a.from, want = a.want, nvec = (sl + 15) / 16;
+  const int c0 = static_cast<int>(from / sl), c1 = static_cast<int>((from + want - 1) / sl);
+  const EcReadCol first = ec_read_col(sl, from, want, c0), last = ec_read_col(sl, from, want, c1);
+  const uint64_t f0 = first.first_step(), l0 = first.last_step(), f1 = last.first_step(), l1 = last.last_step();
+  // does data column c want wave step s (the columns between c0 and c1 want every step there is)
+  auto wants = [&](int c, uint64_t s) {
+    return c >= c0 && c <= c1 && (c != c0 || (s >= f0 && s <= l0)) && (c != c1 || (s >= f1 && s <= l1));
+  };
+  auto load = [&](int j, uint64_t v) {
+    uint4 d = make_uint4(0, 0, 0, 0);
+    if (v < nvec) {
+      const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.in[j]) + v);
+      d = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    return d;
+  };
+  auto store = [&](int c, uint64_t v, const uint4& cur, const uint4& below) {
+    const EcReadCol cr = ec_read_col(sl, from, want, c);
+    const int64_t delta = static_cast<int64_t>(c * sl) - static_cast<int64_t>(from);
+    shift_store(a.out, delta, delta + static_cast<int64_t>(cr.lo), delta + static_cast<int64_t>(cr.hi),
+                static_cast<int64_t>(v), cur, below);
+  };
+  bool carried_shift = false;  // does a rebuilt column sit at a byte shift (its lane 0 needs the vector below)
+#pragma unroll
+  for (int r = 0; r < R; ++r) carried_shift = carried_shift || ((a.row_col[r] * sl - from) & 15) != 0;
+
+  const uint64_t total = a.seg_steps[0] + a.seg_steps[1], nwaves = gridDim.x * 4ull, gw = blockIdx.x * 4ull + wave;
+  const uint64_t i_begin = gw * total / nwaves, i_end = (gw + 1) * total / nwaves;
+  uint4 carry[RR];  // lane 63's rebuilt vectors of step carry_step: wave-uniform
+#pragma unroll
+  for (int r = 0; r < RR; ++r) carry[r] = make_uint4(0, 0, 0, 0);
+  uint64_t carry_step = ~0ull - 1;
+  for (uint64_t i = i_begin; i < i_end; ++i) {
+    const uint64_t s = i < a.seg_steps[0] ? a.seg_begin[0] + i : a.seg_begin[1] + (i - a.seg_steps[0]);
+    uint32_t copy_mask = 0, row_mask = 0;
+    for (int j = 0; j < k; ++j)
+      if (wants(a.surv_col[j], s)) copy_mask |= 1u << j;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (wants(a.row_col[r], s)) row_mask |= 1u << r;
+    uint32_t rest = row_mask ? (k >= 32 ? ~0u : (1u << k) - 1u) : copy_mask;
+    if (!rest) continue;
+    const uint64_t v0 = s * 64, v = v0 + lane;
+
+    uint4 acc[RR];
+    if constexpr (R > 0) {
+      if (row_mask && carried_shift && v0 > 0 && carry_step + 1 != s) {
+        // start of a run: rebuild the one vector below lane 0 (every lane loads the same 16 B)
+#pragma unroll
+        for (int r = 0; r < R; ++r) carry[r] = make_uint4(0, 0, 0, 0);
+        for (int j = 0; j < k; ++j) gf_accumulate16<R>(gft, k, j, load(j, v0 - 1), carry);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          carry[r] = make_uint4(__builtin_amdgcn_readfirstlane(carry[r].x), __builtin_amdgcn_readfirstlane(carry[r].y),
+                                __builtin_amdgcn_readfirstlane(carry[r].z), __builtin_amdgcn_readfirstlane(carry[r].w));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r] = make_uint4(0, 0, 0, 0);
+    }
+
+    int j = __builtin_ctz(rest);
+    rest &= rest - 1;
+    // the vector below lane 0's, for a copied column at a byte shift: one extra load in one lane
+    auto load_below = [&](int jj) {
+      return lane == 0 && v0 > 0 && ((copy_mask >> jj) & 1u) ? load(jj, v0 - 1) : make_uint4(0, 0, 0, 0);
+    };
+    uint4 cur = load(j, v), below = load_below(j);
+    for (;;) {
+      const int jn = rest ? __builtin_ctz(rest) : -1;
+      uint4 nxt, nxt_below;
+      if (jn >= 0) {
+        nxt = load(jn, v);
+        nxt_below = load_below(jn);
+      }
+      if ((copy_mask >> j) & 1u) store(a.surv_col[j], v, cur, below);
+      if constexpr (R > 0)
+        if (row_mask) gf_accumulate16<R>(gft, k, j, cur, acc);
+      if (jn < 0) break;
+      rest &= rest - 1;
+      j = jn;
+      cur = nxt;
+      below = nxt_below;
+    }
+    if constexpr (R > 0) {
+      if (row_mask) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          if ((row_mask >> r) & 1u) store(a.row_col[r], v, acc[r], carry[r]);
+          carry[r] = make_uint4(__builtin_amdgcn_readlane(acc[r].x, 63), __builtin_amdgcn_readlane(acc[r].y, 63),
+                                __builtin_amdgcn_readlane(acc[r].z, 63), __builtin_amdgcn_readlane(acc[r].w, 63));
+        }
+        carry_step = s;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -1769,6 +1982,59 @@ hipError_t launch_ec_fused(const EcFusedLaunch& a, const DevCrcTables* t, int gr
     case 7: hipLaunchKernelGGL((ec_fused_kernel<3, true>), g, b, 0, s, a, t); break;
     case 8: hipLaunchKernelGGL((ec_fused_kernel<4, false>), g, b, 0, s, a, t); break;
     default: hipLaunchKernelGGL((ec_fused_kernel<4, true>), g, b, 0, s, a, t); break;
+  }
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_ec_read_fused{-1};
+
+void set_ec_read_fused(bool on) { g_ec_read_fused.store(on ? 1 : 0); }
+
+bool ec_read_fused_enabled() {
+  int v = g_ec_read_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_EC_READ_FUSED");
+    g_ec_read_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+hipError_t launch_ec_read(const EcReadLaunch& in, hipStream_t s) {
+  EcReadLaunch a = in;
+  if (a.k <= 0 || a.k > kMaxShards || a.rows < 0 || a.rows > kEcFusedMaxRows || a.sl < kEcReadMinShard || a.want == 0 ||
+      a.from + a.want > a.sl * a.k || !a.out || (a.rows && !a.tables))
+    return hipErrorInvalidValue;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.tables);
+  for (int j = 0; j < a.k; ++j) {
+    if (!a.in[j] || a.surv_col[j] >= a.k) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(a.in[j]);
+  }
+  for (int r = 0; r < a.rows; ++r)
+    if (a.row_col[r] < 0 || a.row_col[r] >= a.k) return hipErrorInvalidValue;
+  if (bits % 16) return hipErrorInvalidValue;
+  // The steps some column wants. Three or more columns: the middle ones want the whole shard.
+  // Two: the tail of the first and the head of the second, which may leave a gap. One: its own.
+  const uint64_t c0 = a.from / a.sl, c1 = (a.from + a.want - 1) / a.sl;
+  const EcReadCol first = ec_read_col(a.sl, a.from, a.want, c0), last = ec_read_col(a.sl, a.from, a.want, c1);
+  a.seg_begin[0] = a.seg_begin[1] = a.seg_steps[0] = a.seg_steps[1] = 0;
+  if (c1 == c0 + 1 && last.last_step() + 1 < first.first_step()) {
+    a.seg_steps[0] = last.last_step() + 1;
+    a.seg_begin[1] = first.first_step();
+    a.seg_steps[1] = first.last_step() + 1 - first.first_step();
+  } else {
+    a.seg_begin[0] = c1 > c0 ? 0 : first.first_step();
+    a.seg_steps[0] = first.last_step() + 1 - a.seg_begin[0];  // the first column reaches the shard's end, or is the only one
+  }
+  // at least two steps per wave: a run's first step of a rebuilt column pays for the vector below it
+  const uint64_t total = a.seg_steps[0] + a.seg_steps[1], want_wg = (total + 7) / 8;
+  const dim3 g(static_cast<unsigned>(want_wg < static_cast<uint64_t>(kEcReadMaxGrid) ? want_wg : kEcReadMaxGrid)),
+      b(kCrcWgThreads);
+  switch (a.rows) {
+    case 0: hipLaunchKernelGGL(ec_read_kernel<0>, g, b, 0, s, a); break;
+    case 1: hipLaunchKernelGGL(ec_read_kernel<1>, g, b, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(ec_read_kernel<2>, g, b, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(ec_read_kernel<3>, g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL(ec_read_kernel<4>, g, b, 0, s, a); break;
   }
   return hipGetLastError();
 }

@@ -573,6 +573,100 @@ static int ec_fused_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// --ec-convert: the tiering conversion of a resident block (ENCODE_EC) three ways, alternating in
+// every repetition: ChunkStore::ec_encode_block on the single kernel, the same call staged (one
+// copy per column, K4, one K2 launch per shard), and the host route it replaces (verified read to
+// the host, split into padded columns, gf_matmul_gpu, k + m CPU CRCs). Block sizes are a few
+// bytes under 1, 16 and 100 MiB so that sl % 16 != 0 and the last column is short. One JSON line
+// per (k, m, size) cell; times are microseconds per block, each the mean of `iters` back-to-back
+// conversions (every one ends in a stream synchronise).
+static int ec_convert_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--ec-convert needs a GPU\n");
+    return 1;
+  }
+  std::filesystem::remove_all(dir);
+  StoreConfig cfg;
+  cfg.storage_dir = dir + "/ecc";
+  cfg.device = device;
+  cfg.hbm_capacity = 2ull << 30;
+  ChunkStore s(cfg);
+  const int shapes[][2] = {{6, 3}, {10, 4}};
+  int rc = 0;
+  for (auto& km : shapes)
+    for (uint64_t mib : {1ull, 16ull, 100ull}) {
+      const int k = km[0], m = km[1];
+      uint64_t n = (mib << 20) - 7;
+      while (((n + k - 1) / k) % 16 == 0) --n;
+      const uint64_t sl = (n + k - 1) / k;
+      const auto data = random_bytes(n, static_cast<uint32_t>(k * 131 + mib));
+      const std::string id = "conv";
+      if (!s.write(id, data.data(), n, crc32(data.data(), n)).ok) return 1;
+      gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+      const int iters = static_cast<int>(std::clamp<uint64_t>((256ull << 20) / n, 2, 50));
+      std::vector<uint32_t> crcs[3];
+      std::vector<double> us[3];  // [0] host route, [1] staged, [2] fused
+      bool ok = true;
+      auto host_route = [&] {
+        std::vector<uint8_t> blk(n);
+        ReadResult r = s.read_into(id, 0, n, blk.data());
+        if (r.status != ReadStatus::Ok || r.bytes != n) return false;
+        std::vector<std::vector<uint8_t>> sh(k + m, std::vector<uint8_t>(sl, 0));
+        for (int c = 0; c < k; ++c)
+          if (c * sl < n) std::memcpy(sh[c].data(), blk.data() + c * sl, std::min(sl, n - c * sl));
+        std::vector<const uint8_t*> in;
+        std::vector<uint8_t*> out;
+        for (int c = 0; c < k; ++c) in.push_back(sh[c].data());
+        for (int r2 = 0; r2 < m; ++r2) out.push_back(sh[k + r2].data());
+        if (!s.gf_matmul_gpu(parity, in, out, sl)) return false;
+        crcs[0].clear();
+        for (auto& v : sh) crcs[0].push_back(crc32(v.data(), sl));
+        return true;
+      };
+      auto run = [&](int mode, int cnt) {
+        set_ec_convert_fused(mode == 2);
+        const auto t0 = Clock::now();
+        for (int i = 0; i < cnt && ok; ++i) {
+          if (mode == 0) {
+            ok = host_route();
+            continue;
+          }
+          ChunkStore::EcBuffers enc;
+          std::string err;
+          ok = s.ec_encode_block(id, k, parity, &enc, &err);
+          if (ok) crcs[mode] = enc.crc;
+          s.ec_free(&enc);
+        }
+        return secs(t0, Clock::now()) * 1e6 / cnt;
+      };
+      for (int mode = 0; mode < 3; ++mode) run(mode, 2);  // warm-up: code objects, scratch, extents
+      const uint64_t before = s.stats().ec_fused_converts;
+      for (int rep = 0; rep < reps; ++rep)
+        for (int mode = 2; mode >= 0; --mode) us[mode].push_back(run(mode, iters));
+      const uint64_t fused_runs = s.stats().ec_fused_converts - before;
+      auto list = [](const std::vector<double>& v) {
+        std::string o;
+        for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+        return o;
+      };
+      auto least = [](const std::vector<double>& v) { return *std::min_element(v.begin(), v.end()); };
+      const bool match = ok && crcs[0] == crcs[1] && crcs[1] == crcs[2] && fused_runs == static_cast<uint64_t>(reps) * iters;
+      std::printf("{\"ec_convert\": {\"k\": %d, \"m\": %d, \"block_bytes\": %llu, \"shard_len\": %llu, \"iters\": %d, "
+                  "\"fused_us\": [%s], \"staged_us\": [%s], \"host_us\": [%s], \"fused_min_us\": %.1f, "
+                  "\"staged_min_us\": %.1f, \"host_min_us\": %.1f, \"match\": %s}}\n",
+                  k, m, static_cast<unsigned long long>(n), static_cast<unsigned long long>(sl), iters, list(us[2]).c_str(),
+                  list(us[1]).c_str(), list(us[0]).c_str(), least(us[2]), least(us[1]), least(us[0]),
+                  match ? "true" : "false");
+      std::fflush(stdout);
+      if (!match) rc = 1;
+      s.remove(id);
+    }
+  set_ec_convert_fused(true);
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 // --ec-read: ChunkStore::ec_read_range of a resident RS(6,3) file with 1 and 2 lost data columns
 // into a registered buffer: the whole file and a 64 KiB range inside the first lost column, the
 // single-kernel path against the staged one (ec_decode into HBM, then one copy per column),
@@ -683,6 +777,17 @@ int main(int argc, char** argv) {
         if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
       }
       return ec_read_bench(device, dir, std::max(1, reps));
+    }
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--ec-convert") {
+      std::string dir = "/tmp/io_bench_ecc";
+      int device = 0, reps = 3;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return ec_convert_bench(device, dir, std::max(1, reps));
     }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--ec-fused") {

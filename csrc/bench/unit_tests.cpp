@@ -208,6 +208,26 @@ TEST(crc32_golden_combine_and_slices) {
   CHECK(crc32_from_slices(sl.data(), buf.size()) == whole);
 }
 
+// The source check of the device EC conversion (ChunkStore::ec_encode_block): the CRCs of the k
+// zero-padded columns of a block fold into the block's CRC extended by the padding.
+TEST(crc32_of_padded_columns_folds_to_the_block_crc) {
+  std::mt19937 g(2);
+  const uint8_t zeros[32] = {};
+  for (auto [k, n] : {std::pair<int, size_t>{2, 1}, {4, 5}, {4, 2048}, {3, 1580}, {10, 655383}}) {
+    std::vector<uint8_t> buf(n);
+    for (auto& b : buf) b = static_cast<uint8_t>(g());
+    const size_t sl = (n + k - 1) / k, pad = k * sl - n;
+    std::vector<uint8_t> padded(buf);
+    padded.resize(k * sl, 0);
+    uint32_t folded = crc32(padded.data(), sl);
+    for (int c = 1; c < k; ++c) folded = crc32_combine(folded, crc32(padded.data() + c * sl, sl), sl);
+    CHECK(pad < static_cast<size_t>(k));
+    CHECK(folded == crc32_combine(crc32(buf.data(), n), crc32(zeros, pad), pad));
+    buf[n / 2] ^= 0xFF;  // what the device would have read from a corrupt extent
+    CHECK(folded != crc32_combine(crc32(buf.data(), n), crc32(zeros, pad), pad));
+  }
+}
+
 // ------------------------------------------------------------------------------- erasure
 TEST(reed_solomon_recovers_any_m_losses) {
   const int k = 4, m = 2;

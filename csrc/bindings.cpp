@@ -243,6 +243,8 @@ PYBIND11_MODULE(_dfs_native, m) {
   m.def("crc_wide_mode", &crc_wide_mode);
   m.def("crc_fp4_enabled", &crc_fp4_enabled);
   m.def("set_crc_fp4", &set_crc_fp4, "wide K1/K2: chunk CRCs on the FP4 matrix cores (else i8)");
+  m.def("set_ec_convert_fused", &set_ec_convert_fused,
+        "EC conversion of a resident block in one kernel (else one copy per column, K4, K2 per shard)");
   m.def("set_ec_fused", &set_ec_fused, "device EC in one fused kernel per stripe (else copies, K4/K5, K2 per shard)");
   m.def("set_ec_read_fused", &set_ec_read_fused, "degraded EC range reads in one kernel (else decode into HBM, then copies)");
   m.def("set_crc_wide", &set_crc_wide, "K1/K2 one workgroup per CU: 0 off, 1 shared LDS image, 2 + LDS basis");
@@ -477,6 +479,22 @@ PYBIND11_MODULE(_dfs_native, m) {
         if (!ok) return py::none();
         return ec_result(s, &enc);
       }, py::arg("buffer"), py::arg("k"), py::arg("m"), py::arg("shard_len"), py::arg("stride"))
+      // the tiering conversion: the resident block -> its k data and m parity shards of
+      // ceil(size / k) bytes, as [(shard, crc32, .meta image)]; None on failure (not resident,
+      // arena full, or the bytes in HBM no longer match the block's checksum)
+      .def("ec_encode_block", [](ChunkStore& s, const std::string& block_id, int k, int m) -> py::object {
+        if (k <= 0 || m <= 0) throw std::invalid_argument("ec_encode_block: k and m must be positive");
+        gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+        ChunkStore::EcBuffers enc;
+        std::string err;
+        bool ok;
+        {
+          py::gil_scoped_release rel;
+          ok = s.ec_encode_block(block_id, k, parity, &enc, &err);
+        }
+        if (!ok) return py::none();
+        return ec_result(s, &enc);
+      }, py::arg("block_id"), py::arg("k"), py::arg("m"))
       // rows x the resident blocks `block_ids` (each shard_len bytes) -> the rebuilt shards
       .def("ec_decode", [](ChunkStore& s, std::vector<std::vector<int>> rows, std::vector<std::string> block_ids,
                            uint64_t shard_len) -> py::object {

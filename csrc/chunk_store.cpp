@@ -2555,6 +2555,7 @@ StoreStats ChunkStore::stats() {
   s.fused_reads = fused_reads_.load();
   s.fused_writes = fused_writes_.load();
   s.ec_fused_encodes = ec_fused_encodes_.load();
+  s.ec_fused_converts = ec_fused_converts_.load();
   s.ec_fused_decodes = ec_fused_decodes_.load();
   s.ec_fused_reads = ec_fused_reads_.load();
   s.pulled_recvs = pulled_recvs_.load();
@@ -3685,7 +3686,7 @@ bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }  // namespace
 
 bool ChunkStore::ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
-                          std::vector<uint32_t>* crc, std::string* err) {
+                          std::vector<uint32_t>* crc, std::string* err, const uint8_t* block, uint64_t n) {
   const int nsh = (a.encode ? a.k : 0) + a.rows;
   const CrcPlan p = plan_crc(nullptr, len, nullptr, nullptr, true, 0, len);
   a.s_full = p.a.s_full;
@@ -3702,8 +3703,9 @@ bool ChunkStore::ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vect
   a.part_crc = reinterpret_cast<uint32_t*>(hdev);
   a.tail_be = reinterpret_cast<uint32_t*>(hdev + ec_fused_tail_off(nsh));
   a.tables = reinterpret_cast<const uint32_t*>(hdev + ec_fused_table_off(nsh));
-  const int grid = ec_fused_grid(a.ntiles, a.tail_len, a.rows);
-  const hipError_t e = launch_ec_fused(a, dtables_, grid, l->stream);
+  const int grid = block ? ec_convert_grid(a.ntiles, a.tail_len, a.rows) : ec_fused_grid(a.ntiles, a.tail_len, a.rows);
+  const hipError_t e = block ? launch_ec_convert(EcConvertLaunch{a, block, n, len}, dtables_, grid, l->stream)
+                             : launch_ec_fused(a, dtables_, grid, l->stream);
   launches_++;
   if (e != hipSuccess) {
     *err = std::string("fused EC kernel launch: ") + hipGetErrorString(e);
@@ -3801,6 +3803,106 @@ bool ChunkStore::ec_encode(const uint8_t* host, uint64_t host_stride, uint64_t l
   }
   out->ext = ext;
   out->len = len;
+  out->stride = stride;
+  out->meta_stride = ms;
+  out->count = total;
+  return true;
+}
+
+bool ChunkStore::ec_encode_block(const std::string& id, int k, const std::vector<std::vector<uint8_t>>& parity,
+                                 EcBuffers* out, std::string* err) {
+  TraceRange tr("dfs.store.ec_encode_block");
+  const int m = static_cast<int>(parity.size()), total = k + m;
+  if (!gpu() || k <= 0 || m <= 0 || k > kMaxShards || m > kMaxShards) {
+    *err = "device EC needs a GPU store and 1..32 shards";
+    return false;
+  }
+  HIP_OK(hipSetDevice(cfg_.device));
+  uint64_t n = 0;
+  const uint8_t* src = pin_device(id, &n);
+  if (!src || n == 0) {
+    if (src) unpin(id);
+    *err = "EC conversion: block not resident or empty";
+    return false;
+  }
+  const uint64_t sl = (n + k - 1) / k, stride = align_up(std::max<uint64_t>(sl, 16), 256), ms = ec_meta_stride(sl);
+  const uint64_t tbytes = static_cast<uint64_t>(m) * k * 32;
+  DevExtent ext = reserve(stride * total + ms * total + align_up(tbytes, 256));
+  bool ok = ext.off >= 0;
+  if (!ok) *err = "HBM arena full";
+  if (ok) {
+    uint8_t* metas = ext.ptr + stride * total;
+    auto* dtab = reinterpret_cast<uint32_t*>(metas + ms * total);
+    Lane* l = acquire_lane();
+    const bool fused = m <= kEcFusedMaxRows && total <= kMaxShards && ec_convert_fused_enabled() && crc_mfma_enabled() &&
+                       aligned16(src);
+    ensure_hscratch(l, fused ? ec_fused_table_off(total) + tbytes : tbytes + 16);
+    if (fused && l->hscratch_dev) {
+      EcFusedLaunch a{};
+      a.k = k;
+      a.rows = m;
+      a.encode = true;
+      for (int c = 0; c < k; ++c) a.dst[c] = ext.ptr + c * stride;
+      for (int r = 0; r < m; ++r) a.out[r] = ext.ptr + (k + r) * stride;
+      for (int i = 0; i < total; ++i) a.meta[i] = reinterpret_cast<uint32_t*>(metas + i * ms);
+      ok = ec_fused(l, a, parity, sl, &out->crc, err, src, n);
+      if (ok) ec_fused_converts_++;
+    } else {
+      std::vector<uint8_t> flat(static_cast<size_t>(m) * k);
+      for (int r = 0; r < m; ++r)
+        for (int c = 0; c < k; ++c) flat[r * k + c] = parity[r][c];
+      auto* htab = reinterpret_cast<uint32_t*>(l->hscratch + 2 * kMaxGridCrc * sizeof(uint32_t) + 16);
+      gf_nibble_tables(flat.data(), m, k, htab);
+      HIP_OK(hipMemcpyAsync(dtab, htab, tbytes, hipMemcpyHostToDevice, l->stream));
+      for (int c = 0; c < k; ++c) {  // column c of the block, zeros from the block's end on
+        const uint64_t at = c * sl, have = at < n ? std::min(sl, n - at) : 0;
+        if (have) HIP_OK(hipMemcpyAsync(ext.ptr + c * stride, src + at, have, hipMemcpyDeviceToDevice, l->stream));
+        if (have < sl) HIP_OK(hipMemsetAsync(ext.ptr + c * stride + have, 0, sl - have, l->stream));
+      }
+      GfLaunch a{};
+      a.k = k;
+      a.rows = m;
+      a.len = sl;
+      a.tables = dtab;
+      for (int c = 0; c < k; ++c) a.in[c] = ext.ptr + c * stride;
+      for (int r = 0; r < m; ++r) a.out[r] = ext.ptr + (k + r) * stride;
+      ok = launch_gf_matmul(a, l->stream) == hipSuccess;
+      launches_++;
+      out->crc.assign(total, 0);
+      for (int i = 0; ok && i < total; ++i) {
+        CrcOut co;
+        ok = run_crc(l, ext.ptr + i * stride, sl, reinterpret_cast<uint32_t*>(metas + i * ms), nullptr, true, 0, sl, &co,
+                     err);
+        out->crc[i] = co.block_crc;
+      }
+    }
+    if (ok) {
+      // This stands in for a verifying read of the source: the data shards' CRCs, folded, are the
+      // CRC of what the device really read (block || zeros); no second pass over the bytes.
+      const uint64_t pad = k * sl - n;  // < k
+      const uint8_t zeros[kMaxShards] = {};
+      uint32_t got = out->crc[0];
+      for (int c = 1; c < k; ++c) got = crc32_combine(got, out->crc[c], sl);
+      if (got != crc32_combine(block_crc(id), crc32(zeros, pad), pad)) {
+        *err = kEcSourceCorrupt;
+        ok = false;
+      }
+    }
+    if (ok) {
+      HIP_OK(hipEventCreateWithFlags(&out->done, hipEventDisableTiming));
+      HIP_OK(hipEventRecord(out->done, l->stream));
+      HIP_OK(hipStreamSynchronize(l->stream));
+    }
+    release_lane(l);
+  }
+  unpin(id);
+  if (!ok) {
+    if (ext.off >= 0) release(ext);
+    if (err->empty()) *err = "GPU erasure coding failed";
+    return false;
+  }
+  out->ext = ext;
+  out->len = sl;
   out->stride = stride;
   out->meta_stride = ms;
   out->count = total;

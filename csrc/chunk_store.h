@@ -92,6 +92,7 @@ struct StoreStats {
   uint64_t fused_reads = 0;      // reads delivered by the K3 verify+copy kernel (no SDMA copy)
   uint64_t fused_writes = 0;     // writes staged by the K1/K2 copy+checksum kernel (no SDMA copy)
   uint64_t ec_fused_encodes = 0;  // RS stripes landed, encoded and checksummed by one ec_fused_kernel launch
+  uint64_t ec_fused_converts = 0;  // resident blocks turned into RS shards by one ec_convert_kernel launch
   uint64_t ec_fused_decodes = 0;  // shard sets rebuilt and checksummed by one ec_fused_kernel launch
   uint64_t ec_fused_reads = 0;    // degraded EC range reads served by one ec_read_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
@@ -288,6 +289,17 @@ class ChunkStore {
   // each) into HBM, the rows of `parity` x data computed next to them: out holds k + rows shards.
   bool ec_encode(const uint8_t* host, uint64_t host_stride, uint64_t len, int k,
                  const std::vector<std::vector<uint8_t>>& parity, EcBuffers* out, std::string* err);
+  // The tiering conversion: the resident block `id` (n bytes) -> the k data shards of
+  // sl = ceil(n / k) bytes (block bytes [c * sl, c * sl + sl), zeros from n on) and the rows of
+  // `parity` x those, all in HBM. Up to kEcFusedMaxRows parity rows: one ec_convert_kernel launch
+  // that loads the columns at their byte shifts. Otherwise (or DFS_EC_CONVERT_FUSED=0) staged: one
+  // copy per column, K4, one K2 launch per shard. The block is not read a second time to verify
+  // it: CRC-32 is linear, so the k data-shard CRCs fold into the CRC of block || zeros, which must
+  // equal the stored block CRC extended by the same zeros. If not, the bytes in HBM are not what
+  // was written: false with *err == kEcSourceCorrupt, and no shard exists.
+  static constexpr const char* kEcSourceCorrupt = "EC conversion: the resident block does not match its checksum";
+  bool ec_encode_block(const std::string& id, int k, const std::vector<std::vector<uint8_t>>& parity, EcBuffers* out,
+                       std::string* err);
   // `rows` x the k device inputs -> rows new shards in HBM.
   bool ec_decode(const std::vector<std::vector<uint8_t>>& rows, const std::vector<const uint8_t*>& in, uint64_t len,
                  EcBuffers* out, std::string* err);
@@ -498,10 +510,12 @@ class ChunkStore {
   bool write_copy(Lane* l, const uint8_t* src_dev, uint8_t* dst, uint64_t n, uint32_t* dmeta, uint8_t* hmeta,
                   CrcOut* out, std::string* err);
   // One ec_fused_kernel launch and stream sync for the stripe described by `a` (pointers, k, rows,
-  // encode set by the caller), then the per-shard combine of the whole-shard CRCs into `crc`.
+  // encode set by the caller), then the per-shard combine of the whole-shard CRCs into `crc`. With
+  // `block`: one ec_convert_kernel launch instead, whose data shards are cut from that resident
+  // block of n bytes.
   bool ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
-                std::vector<uint32_t>* crc, std::string* err);
-  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0};
+                std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
+  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

@@ -421,6 +421,43 @@ bool CsAgent::encode_ec(const pb::ChunkServerCommand& c) {
   const int k = c.ec_data_shards, m = c.ec_parity_shards;
   if (k <= 0 || m <= 0 || static_cast<int>(c.ec_shard_sources.size()) != k + m || c.new_block_id.empty())
     return false;
+  gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+  // Device path: the resident block becomes k + m checksummed shards in HBM in one kernel
+  // (ChunkStore::ec_encode_block, which also checks the source against its block CRC). Our own
+  // shards are committed from HBM; the others cross to the host once, with the kernel's CRC.
+  if (store_->gpu()) {
+    ChunkStore::EcBuffers enc;
+    std::string err;
+    if (store_->ec_encode_block(c.block_id, k, parity, &enc, &err)) {
+      const uint64_t sl = enc.len;
+      std::vector<std::future<bool>> futs;
+      for (int i = 0; i < k + m; ++i)
+        futs.push_back(jobs_.submit([this, i, sl, &enc, &c] {
+          if (is_me(c.ec_shard_sources[i]))
+            return store_->commit_copy(c.new_block_id, enc.shard(i), sl, enc.crc[i], true).ok;
+          std::vector<uint8_t> shard(sl);
+          if (!store_->device_to_host(shard.data(), enc.shard(i), sl)) return false;
+          pb::WriteBlockRequest q;
+          q.block_id = c.new_block_id;
+          q.expected_checksum_crc32c = enc.crc[i];
+          q.shard_index = i;
+          q.master_term = c.master_term;
+          GrpcResult r = pool_.call(target(c.ec_shard_sources[i]), "/dfs.ChunkServerService/WriteBlock",
+                                    encode_with_payload(q, shard.data(), shard.size()), rid());
+          pb::WriteBlockResponse resp;
+          return r.transport_ok && r.status == 0 && resp.decode(r.message) && resp.success;
+        }));
+      bool ok = true;
+      for (auto& f : futs) ok = f.get() && ok;
+      store_->ec_free(&enc);
+      std::lock_guard<std::mutex> g(mu_);
+      st_.ec_gpu++;
+      st_.encode_device++;
+      return ok;
+    }
+    // corrupt in HBM: the scrubber or the recovery path owns the block, not a host re-read here
+    if (err == ChunkStore::kEcSourceCorrupt) return false;
+  }
   std::vector<uint8_t> data;
   if (!read_local(c.block_id, &data) || data.empty()) return false;
   const uint64_t sl = (data.size() + k - 1) / k;
@@ -429,7 +466,6 @@ bool CsAgent::encode_ec(const pb::ChunkServerCommand& c) {
     const uint64_t off = static_cast<uint64_t>(i) * sl;
     if (off < data.size()) std::memcpy(shards[i].data(), data.data() + off, std::min<uint64_t>(sl, data.size() - off));
   }
-  gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
   std::vector<const uint8_t*> in;
   std::vector<uint8_t*> out;
   for (int i = 0; i < k; ++i) in.push_back(shards[i].data());

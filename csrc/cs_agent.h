@@ -14,8 +14,11 @@
 //                                 otherwise;
 //                     RECONSTRUCT_EC_SHARD  parallel ReadBlock of the survivors, GF(2^8)
 //                                 decode on the GPU (CPU codec without one), local write;
-//                     ENCODE_EC   RS encode of the verified local replica, k+m shard writes
-//                                 in parallel (tiering, C32);
+//                     ENCODE_EC   RS(k, m) of the local replica, k+m shard writes in parallel
+//                                 (tiering, C32): a block resident in HBM is cut, encoded and
+//                                 checksummed there by one kernel, which also checks it against
+//                                 its block CRC; otherwise a verified read to the host, the GF
+//                                 product on the GPU (CPU codec without one) and CPU checksums;
 //                     DELETE / MOVE_TO_COLD  store operations;
 //                     recovery    of a corrupt block: ReadBlock from another holder, checked
 //                                 against OUR .meta (reference: the replica must match what
@@ -61,6 +64,7 @@ struct CsAgentStats {
   uint64_t replicate_engine = 0, replicate_grpc = 0, replicate_failed = 0;
   uint64_t reconstructs = 0, reconstruct_failed = 0, encodes = 0, encode_failed = 0;
   uint64_t reconstruct_device = 0;  // of the reconstructs: gathered into HBM and decoded there
+  uint64_t encode_device = 0;       // of the encodes: converted from the resident block in HBM
   uint64_t recoveries = 0, recovery_failed = 0, deletes = 0, moves = 0, scrubs = 0, scrub_bad = 0;
   uint64_t ec_gpu = 0, ec_cpu = 0;
 };

@@ -37,6 +37,7 @@ Json stats_json(const StoreStats& t) {
   d.set("fused_reads", t.fused_reads);
   d.set("fused_writes", t.fused_writes);
   d.set("ec_fused_encodes", t.ec_fused_encodes);
+  d.set("ec_fused_converts", t.ec_fused_converts);
   d.set("ec_fused_decodes", t.ec_fused_decodes);
   d.set("ec_fused_reads", t.ec_fused_reads);
   d.set("pulled_recvs", t.pulled_recvs);
@@ -107,6 +108,7 @@ Json stats_json(const CsAgentStats& t) {
   d.set("agent_replicate_failed", t.replicate_failed);
   d.set("agent_reconstructs", t.reconstructs);
   d.set("agent_reconstruct_device", t.reconstruct_device);
+  d.set("agent_encode_device", t.encode_device);
   d.set("agent_reconstruct_failed", t.reconstruct_failed);
   d.set("agent_encodes", t.encodes);
   d.set("agent_encode_failed", t.encode_failed);

@@ -8,6 +8,9 @@
 //          reference erasure.rs:7-49).
 //   K4/K5 + K2  ec_fused_kernel: a whole RS stripe in one pass — the shards are landed (encode),
 //          multiplied and checksummed from the registers they were loaded or computed in.
+//   K4 + K2 of a resident block  ec_convert_kernel: the tiering conversion — the block's columns
+//          are loaded at their byte shifts, zero-padded behind the block's end, and leave as k + m
+//          stored and checksummed shards in the fused kernel's encode form.
 //   K5 + range read  ec_read_kernel: a byte range of an RS-coded file whose data shards are partly
 //          lost — only the lost columns inside the range are rebuilt, and the bytes go from the
 //          registers over PCIe into the reader's registered buffer.
@@ -192,6 +195,25 @@ bool ec_fused_enabled();
 void set_ec_fused(bool on);
 int ec_fused_grid(uint64_t ntiles, uint32_t tail_len, int rows);
 hipError_t launch_ec_fused(const EcFusedLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// K4 + K2 of the tiering conversion (ec_convert_kernel): one launch turns the resident block `src`
+// (HBM, 16 B aligned, n >= 1 bytes in an extent padded to 16 B) into the k + rows shards of
+// RS(k, rows), sl = ceil(n / k) bytes each. Data shard c is block bytes [c * sl, c * sl + sl),
+// zeros from n on: the columns sit at arbitrary byte shifts and the last ones are short or empty.
+// `f` is the encode form of an EcFusedLaunch for shards of sl bytes — `dst` the k data shards,
+// `out` the parity shards, `meta`, the plan, the tables, `part_crc` and `tail_be` as there — with
+// `in` unused. Every pointer is 16 B aligned; rows <= kEcFusedMaxRows, k + rows <= kMaxShards.
+struct EcConvertLaunch {
+  EcFusedLaunch f;
+  const uint8_t* src;
+  uint64_t n, sl;
+};
+// DFS_EC_CONVERT_FUSED=0 keeps the staged conversion (one copy per column, K4, one K2 launch per
+// shard); set_ec_convert_fused is the benches' A/B switch.
+bool ec_convert_fused_enabled();
+void set_ec_convert_fused(bool on);
+int ec_convert_grid(uint64_t ntiles, uint32_t tail_len, int rows);
+hipError_t launch_ec_convert(const EcConvertLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 
 // Degraded range read of an RS(k, m) file (ec_read_kernel): bytes [from, from + want) of the
 // original file — byte x is byte x % sl of data column x / sl — into `out`, the 16 B aligned

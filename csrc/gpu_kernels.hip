@@ -374,8 +374,10 @@ __device__ __forceinline__ void load_lds_image(const DevCrcTables* __restrict__ 
 
 // The short tail slice (len < 512 bytes at `base`) as slice 0 of a wave's 4 KiB, front-padded
 // with zeros to 512 B (the raw CRC ignores leading zeros); every other slice reads as zeros.
-// Byte loads: it runs once per block.
-__device__ __forceinline__ WaveData load_tail_wave(const uint8_t* __restrict__ base, uint32_t len, int lane) {
+// Byte loads: it runs once per block. Only base[0, valid) is read; the bytes behind it count
+// as zeros (a column of a block that ends inside the slice, see ec_convert_kernel).
+__device__ __forceinline__ WaveData load_tail_wave(const uint8_t* __restrict__ base, uint32_t len, int lane,
+                                                   int valid) {
   const int n = lane & 31, h = lane >> 5;
   WaveData d;
 #pragma unroll
@@ -388,7 +390,7 @@ __device__ __forceinline__ WaveData load_tail_wave(const uint8_t* __restrict__ b
       uint32_t v = 0;
       for (int b = 0; b < 4; ++b) {
         const int pos = n * 64 + h * 32 + q * 4 + b;
-        v |= (pos >= pad ? static_cast<uint32_t>(base[pos - pad]) : 0u) << (8 * b);
+        v |= (pos >= pad && pos - pad < valid ? static_cast<uint32_t>(base[pos - pad]) : 0u) << (8 * b);
       }
       w[q] = v;
     }
@@ -396,6 +398,10 @@ __device__ __forceinline__ WaveData load_tail_wave(const uint8_t* __restrict__ b
     d.v[1] = make_uint4(w[4], w[5], w[6], w[7]);
   }
   return d;
+}
+
+__device__ __forceinline__ WaveData load_tail_wave(const uint8_t* __restrict__ base, uint32_t len, int lane) {
+  return load_tail_wave(base, len, lane, static_cast<int>(len));
 }
 
 // Short slice of `len` bytes, front-padded with zeros to 512 B (wave-wide call, lanes 0..7 work).
@@ -1264,10 +1270,10 @@ __global__ __launch_bounds__(256) void gf256_matmul_kernel(GfLaunch a) {
 // R KiB tables + 512 B partials. The compiler's report (-Rpass-analysis=kernel-resource-usage,
 // gfx950; VGPRs + AGPRs / LDS bytes / waves per SIMD; scratch is 0 in all eight):
 //   R  reconstruct             encode
-//   1  177      / 50688 / 2    199      / 50688 / 2
-//   2  196      / 51712 / 2    216      / 51712 / 2
-//   3  238      / 52736 / 2    252      / 52736 / 2
-//   4  256 + 62 / 53760 / 1    256 + 88 / 53760 / 1
+//   1  203      / 50688 / 2    210      / 50688 / 2
+//   2  195      / 51712 / 2    210      / 51712 / 2
+//   3  237      / 52736 / 2    252      / 52736 / 2
+//   4  256 + 62 / 53760 / 1    256 + 86 / 53760 / 1
 template <int R>
 __device__ __forceinline__ void gf_accumulate(const uint32_t* __restrict__ t, int k, int c, const WaveData& d,
                                               WaveData (&pacc)[R]) {
@@ -1308,14 +1314,67 @@ __device__ __forceinline__ void store_tail_wave(uint8_t* __restrict__ base, uint
   }
 }
 
+// The checksum side of the stripe kernels (ec_fused_kernel, ec_convert_kernel) works on the LDS
+// image, the FP4 basis in VGPRs and one running whole-shard partial per wave and shard.
+using StripeParts = uint32_t[4][kMaxShards];
+
+// slice CRCs of the wave's 4 KiB of shard s -> its .meta words and the wave's running partial
+__device__ __forceinline__ void checksum(const EcFusedLaunch& a, const MfmaTileLds& lt, StripeParts& part,
+                                         const ChunkBasis<true>& basis, int s, int64_t i0, const WaveData& d, int lane) {
+  const int wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int64_t hi = static_cast<int64_t>(a.s_full);
+  uint32_t r = slice_from_chunks(lt, basis.crcs(d, lane), lane);
+  const int64_t i = i0 + sw;
+  if (i >= 0 && i < hi && sl == 0) a.meta[s][i] = __builtin_bswap32(r ^ a.full_init);
+  r = combine<8>(r, lane, lt.sh512);
+  r = combine<16>(r, lane, lt.sh1k);
+  r = combine<32>(r, lane, lt.sh2k);
+  const uint32_t acc = mat_apply(lt.tile_pow2[0], part[wave][s], lane) ^ r;
+  if (lane == 0) part[wave][s] = acc;
+}
+
+// the short tail slice of shard s, front-padded in `d`: its .meta word, and the bytes into `shard`
+__device__ __forceinline__ void checksum_tail(const EcFusedLaunch& a, const MfmaTileLds& lt,
+                                              const ChunkBasis<true>& basis, int s, uint8_t* __restrict__ shard,
+                                              const WaveData& d, int lane) {
+  const uint32_t r = slice_from_chunks(lt, basis.crcs(d, lane), lane);
+  if (lane == 0) {
+    const uint32_t be = __builtin_bswap32(r ^ a.tail_init);
+    a.meta[s][a.s_full] = be;
+    a.tail_be[s] = be;
+  }
+  store_tail_wave(shard + a.s_full * 512, a.tail_len, d, lane);
+}
+
+// place the partials in the shard: (3 - wave) sub-tiles of the wave's last tile follow its
+// accumulator (lane s shifts shard s), then — the shifts are linear, so once for the XOR of
+// the four waves — the (ntiles - t_end) whole tiles behind the workgroup's run
+__device__ __forceinline__ void place_partials(const EcFusedLaunch& a, const MfmaTileLds& lt, StripeParts& part, int nsh,
+                                               uint64_t t_begin, uint64_t t_end, int lane) {
+  const int wave = threadIdx.x >> 6;
+  if (lane < nsh) {
+    uint32_t v = part[wave][lane];
+    for (int j = wave; j < 3; ++j) v = tab4(lt.sh4k, v);
+    part[wave][lane] = v;
+  }
+  __syncthreads();
+  for (int s = wave; s < nsh; s += 4) {
+    uint32_t v = part[0][s] ^ part[1][s] ^ part[2][s] ^ part[3][s];
+    uint64_t e = t_begin < t_end ? a.ntiles - t_end : 0;
+    for (int b = 0; e; ++b, e >>= 1)
+      if (e & 1) v = mat_apply(lt.tile_pow2[b], v, lane);
+    if (lane == 0) a.part_crc[s * kMaxGridCrc + blockIdx.x] = v;
+  }
+}
+
 template <int R, bool kEncode>
 __global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(R < 4 ? 2 : 1, R < 4 ? 2 : 1)))
 void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
   static_assert(R >= 1 && R <= kEcFusedMaxRows, "parity accumulators in VGPRs");
   __shared__ MfmaTileLds lt;
+  __shared__ StripeParts part;
   __shared__ uint32_t gft[R * kMaxShards * 8];
-  __shared__ uint32_t part[4][kMaxShards];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int k = a.k, first_out = kEncode ? k : 0, nsh = first_out + R;
   const uint64_t t_begin = tile_run_begin(a.ntiles, blockIdx.x), t_end = tile_run_begin(a.ntiles, blockIdx.x + 1);
   const int64_t hi = static_cast<int64_t>(a.s_full);
@@ -1331,18 +1390,6 @@ void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
   if (threadIdx.x < 4 * kMaxShards) (&part[0][0])[threadIdx.x] = 0;
   __syncthreads();
 
-  // slice CRCs of the wave's 4 KiB of shard s -> its .meta words and the wave's running partial
-  auto checksum = [&](int s, int64_t i0, const WaveData& d) {
-    uint32_t r = slice_from_chunks(lt, basis.crcs(d, lane), lane);
-    const int64_t i = i0 + sw;
-    if (i >= 0 && i < hi && sl == 0) a.meta[s][i] = __builtin_bswap32(r ^ a.full_init);
-    r = combine<8>(r, lane, lt.sh512);
-    r = combine<16>(r, lane, lt.sh1k);
-    r = combine<32>(r, lane, lt.sh2k);
-    const uint32_t acc = mat_apply(lt.tile_pow2[0], part[wave][s], lane) ^ r;
-    if (lane == 0) part[wave][s] = acc;
-  };
-
   for (uint64_t t = t_begin; t < t_end; ++t) {
     const int64_t i0 = first_slice(t);
     WaveData pacc[R];
@@ -1356,7 +1403,7 @@ void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
       if (more) nxt = load_wave(a.in[c + 1 < k ? c + 1 : 0], c + 1 < k ? i0 : first_slice(t + 1), 0, hi, lane);
       if constexpr (kEncode) {
         store_wave_dst(a.dst[c], i0, 0, hi, cur, lane);
-        checksum(c, i0, cur);
+        checksum(a, lt, part, basis, c, i0, cur, lane);
       }
       gf_accumulate<R>(gft, k, c, cur, pacc);
       if (more) cur = nxt;
@@ -1364,21 +1411,12 @@ void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       store_wave_dst(a.out[r], i0, 0, hi, pacc[r], lane);
-      checksum(first_out + r, i0, pacc[r]);
+      checksum(a, lt, part, basis, first_out + r, i0, pacc[r], lane);
     }
   }
 
   if (a.tail_len && blockIdx.x == 0 && wave == 0) {
     const uint64_t off = a.s_full * 512;
-    auto tail = [&](int s, uint8_t* shard, const WaveData& d) {
-      const uint32_t r = slice_from_chunks(lt, basis.crcs(d, lane), lane);
-      if (lane == 0) {
-        const uint32_t be = __builtin_bswap32(r ^ a.tail_init);
-        a.meta[s][a.s_full] = be;
-        a.tail_be[s] = be;
-      }
-      store_tail_wave(shard + off, a.tail_len, d, lane);
-    };
     WaveData pacc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -1386,29 +1424,197 @@ void ec_fused_kernel(EcFusedLaunch a, const DevCrcTables* __restrict__ gt) {
       for (int v = 0; v < 4; ++v) pacc[r].v[v] = make_uint4(0, 0, 0, 0);
     for (int c = 0; c < k; ++c) {
       const WaveData d = load_tail_wave(a.in[c] + off, a.tail_len, lane);
-      if constexpr (kEncode) tail(c, a.dst[c], d);
+      if constexpr (kEncode) checksum_tail(a, lt, basis, c, a.dst[c], d, lane);
       gf_accumulate<R>(gft, k, c, d, pacc);
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) tail(first_out + r, a.out[r], pacc[r]);
+    for (int r = 0; r < R; ++r) checksum_tail(a, lt, basis, first_out + r, a.out[r], pacc[r], lane);
+  }
+  place_partials(a, lt, part, nsh, t_begin, t_end, lane);
+}
+
+// ---------------------------------------------------------------------------------------
+// K4 + K2 for the tiering conversion: one resident, verified block -> the k + R shards of
+// RS(k, R), in ec_fused_kernel's encode form (same tile axis and runs, same stores, checksums,
+// accumulators and partials; the helpers are shared). What differs is where a data shard's bytes
+// come from: column c of the block starts at byte c * sl, an arbitrary byte shift against the
+// 16 B vectors, and the block ends at n, inside or before the last columns.
+//  * Shifted load. The shift (c * sl) & 15 is uniform per column, a scalar. A lane's 32 B of a
+//    pass are covered by three aligned 16 B vectors of the block (two at shift 0), loaded
+//    non-temporal; v_alignbyte_b32 funnels dwords w .. w + 8 of them (w = shift / 4, a uniform
+//    switch) by shift % 4 bytes into the same 32 B that load_wave gives for an aligned shard. The
+//    third vector is the first of the lane's upper neighbour: a line the wave pulls anyway.
+//  * End of the block. A vector at or behind n is not loaded and reads as zeros (nothing at or
+//    beyond align_up(n, 16) is ever touched); the one vector that straddles n is masked
+//    byte-wise after the wait, only in waves whose 4 KiB reach n (a uniform test). A column at
+//    or behind n is all zeros and still stored, checksummed and multiplied: the zero padding is
+//    part of the shards and of their CRCs.
+//  * Pipeline. The next column's (or tile's) raw vectors are in flight behind the current
+//    column's funnel, stores, checksum and GF arithmetic: 24 VGPRs per buffer instead of the fused
+//    kernel's 16. R = 3 does not have them at 2 waves/SIMD: it spills 88 B per lane to scratch,
+//    and still 24 B with the prefetch dropped (loads at the top of the column step). So R = 3 runs
+//    like R = 4, at 1 wave/SIMD with the overflow in AGPRs and the prefetch kept, and both take
+//    half the grid (ec_convert_grid): one workgroup per CU.
+//  * Tail slice: byte loads as load_tail_wave does them, limited to the column's bytes below n.
+// The compiler's report (-Rpass-analysis=kernel-resource-usage, gfx950; VGPRs + AGPRs / LDS bytes
+// / waves per SIMD; scratch is 0 in all four):
+//   R  convert
+//   1  255       / 50688 / 2
+//   2  256       / 51712 / 2
+//   3  256 + 68  / 52736 / 1
+//   4  256 + 110 / 53760 / 1
+struct ShiftedWave {
+  uint4 v[6];  // per MFMA pass the aligned vectors 0, 16 and 32 B from the lane's bytes, rounded down
+};
+
+struct ConvertCol {
+  const uint8_t* base;  // the aligned vector that holds the column's first byte
+  int64_t left;         // block bytes from base on (<= 0: the column starts behind the block)
+  uint32_t shift;       // of the column's first byte inside that vector
+};
+
+__device__ __forceinline__ ConvertCol convert_col(const EcConvertLaunch& a, int c) {
+  const uint64_t b = static_cast<uint64_t>(c) * a.sl, b16 = b & ~15ull;
+  return {a.src + b16, static_cast<int64_t>(a.n) - static_cast<int64_t>(b16),
+          static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(b & 15)))};
+}
+
+__device__ __forceinline__ ShiftedWave load_wave_shifted(const ConvertCol& col, int64_t i0, int64_t hi, int lane) {
+  const int n = lane & 31, h = lane >> 5;
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  ShiftedWave d;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int c = it * 32 + n;
+    const int64_t i = i0 + (c >> 3), off = i * 512 + (c & 7) * 64 + h * 32;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      d.v[3 * it + j] = make_uint4(0, 0, 0, 0);
+      if (i >= 0 && i < hi && off + 16 * j < col.left && (j < 2 || col.shift)) {
+        const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(col.base + off) + j);
+        d.v[3 * it + j] = make_uint4(x[0], x[1], x[2], x[3]);
+      }
+    }
+  }
+  return d;
+}
+
+// keep the low `keep` bytes (any int; <= 0 none, >= 16 all) of a vector
+__device__ __forceinline__ uint4 keep_bytes(const uint4& v, int64_t keep) {
+  const int r = static_cast<int>(keep < 0 ? 0 : keep > 16 ? 16 : keep);
+  auto m = [&](int q) {
+    const int b = r - 4 * q;
+    return b >= 4 ? ~0u : b <= 0 ? 0u : (1u << (8 * b)) - 1u;
+  };
+  return make_uint4(v.x & m(0), v.y & m(1), v.z & m(2), v.w & m(3));
+}
+
+template <int W>
+__device__ __forceinline__ void funnel_at(const uint32_t (&e)[12], uint32_t b, uint4& lo, uint4& hi) {
+  lo = make_uint4(__builtin_amdgcn_alignbyte(e[W + 1], e[W], b), __builtin_amdgcn_alignbyte(e[W + 2], e[W + 1], b),
+                  __builtin_amdgcn_alignbyte(e[W + 3], e[W + 2], b), __builtin_amdgcn_alignbyte(e[W + 4], e[W + 3], b));
+  hi = make_uint4(__builtin_amdgcn_alignbyte(e[W + 5], e[W + 4], b), __builtin_amdgcn_alignbyte(e[W + 6], e[W + 5], b),
+                  __builtin_amdgcn_alignbyte(e[W + 7], e[W + 6], b), __builtin_amdgcn_alignbyte(e[W + 8], e[W + 7], b));
+}
+
+// The loaded vectors -> the wave's 4 KiB of the column in load_wave's layout: zeros behind the
+// block's end, then bytes [shift, shift + 32) of each pass's three vectors.
+__device__ __forceinline__ WaveData shape_wave(const ConvertCol& col, int64_t i0, ShiftedWave r, int lane) {
+  const int n = lane & 31, h = lane >> 5;
+  if (col.left < (i0 + 8) * 512 + 16) {  // uniform: this wave's vectors reach the end of the block
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int c = it * 32 + n;
+      const int64_t off = (i0 + (c >> 3)) * 512 + (c & 7) * 64 + h * 32;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) r.v[3 * it + j] = keep_bytes(r.v[3 * it + j], col.left - off - 16 * j);
+    }
+  }
+  WaveData d;
+  const uint32_t b = col.shift & 3u;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const uint4 &x = r.v[3 * it], &y = r.v[3 * it + 1], &z = r.v[3 * it + 2];
+    const uint32_t e[12] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, z.x, z.y, z.z, z.w};
+    switch (col.shift >> 2) {  // uniform
+      case 0: funnel_at<0>(e, b, d.v[2 * it], d.v[2 * it + 1]); break;  // shift 0: the first two vectors as they are
+      case 1: funnel_at<1>(e, b, d.v[2 * it], d.v[2 * it + 1]); break;
+      case 2: funnel_at<2>(e, b, d.v[2 * it], d.v[2 * it + 1]); break;
+      default: funnel_at<3>(e, b, d.v[2 * it], d.v[2 * it + 1]); break;
+    }
+  }
+  return d;
+}
+
+template <int R>
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(R < 3 ? 2 : 1, R < 3 ? 2 : 1)))
+void ec_convert_kernel(EcConvertLaunch cv, const DevCrcTables* __restrict__ gt) {
+  static_assert(R >= 1 && R <= kEcFusedMaxRows, "parity accumulators in VGPRs");
+  __shared__ MfmaTileLds lt;
+  __shared__ StripeParts part;
+  __shared__ uint32_t gft[R * kMaxShards * 8];
+  const EcFusedLaunch& a = cv.f;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = a.k, nsh = k + R;
+  const uint64_t t_begin = tile_run_begin(a.ntiles, blockIdx.x), t_end = tile_run_begin(a.ntiles, blockIdx.x + 1);
+  const int64_t hi = static_cast<int64_t>(a.s_full);
+  auto first_slice = [&](uint64_t t) {
+    return static_cast<int64_t>(t * kSlicesPerTile + wave * 8) - static_cast<int64_t>(a.vfront);
+  };
+  ShiftedWave cur;
+  if (t_begin < t_end) cur = load_wave_shifted(convert_col(cv, 0), first_slice(t_begin), hi, lane);
+  ChunkBasis<true> basis;
+  basis.load(gt, lane);
+  load_lds_image(gt, &lt);
+  for (int i = threadIdx.x; i < R * k * 8; i += kCrcWgThreads) gft[i] = a.tables[i];
+  if (threadIdx.x < 4 * kMaxShards) (&part[0][0])[threadIdx.x] = 0;
+  __syncthreads();
+
+  for (uint64_t t = t_begin; t < t_end; ++t) {
+    const int64_t i0 = first_slice(t);
+    WaveData pacc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) pacc[r].v[v] = make_uint4(0, 0, 0, 0);
+    for (int c = 0; c < k; ++c) {
+      const ConvertCol col = convert_col(cv, c);
+      const bool more = c + 1 < k || t + 1 < t_end;
+      ShiftedWave nxt;
+      if (more)
+        nxt = load_wave_shifted(convert_col(cv, c + 1 < k ? c + 1 : 0), c + 1 < k ? i0 : first_slice(t + 1), hi, lane);
+      const WaveData d = shape_wave(col, i0, cur, lane);
+      store_wave_dst(a.dst[c], i0, 0, hi, d, lane);
+      checksum(a, lt, part, basis, c, i0, d, lane);
+      gf_accumulate<R>(gft, k, c, d, pacc);
+      if (more) cur = nxt;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      store_wave_dst(a.out[r], i0, 0, hi, pacc[r], lane);
+      checksum(a, lt, part, basis, k + r, i0, pacc[r], lane);
+    }
   }
 
-  // place the partials in the shard: (3 - wave) sub-tiles of the wave's last tile follow its
-  // accumulator (lane s shifts shard s), then — the shifts are linear, so once for the XOR of
-  // the four waves — the (ntiles - t_end) whole tiles behind the workgroup's run
-  if (lane < nsh) {
-    uint32_t v = part[wave][lane];
-    for (int j = wave; j < 3; ++j) v = tab4(lt.sh4k, v);
-    part[wave][lane] = v;
+  if (a.tail_len && blockIdx.x == 0 && wave == 0) {
+    const int64_t off = static_cast<int64_t>(a.s_full * 512);
+    WaveData pacc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) pacc[r].v[v] = make_uint4(0, 0, 0, 0);
+    for (int c = 0; c < k; ++c) {
+      // byte loads at the column's own offset: what is left of the block behind the tail's start
+      const int64_t at = static_cast<int64_t>(c * cv.sl) + off, left = static_cast<int64_t>(cv.n) - at;
+      const WaveData d = load_tail_wave(cv.src + at, a.tail_len, lane,
+                                        static_cast<int>(left < 0 ? 0 : left > 512 ? 512 : left));
+      checksum_tail(a, lt, basis, c, a.dst[c], d, lane);
+      gf_accumulate<R>(gft, k, c, d, pacc);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) checksum_tail(a, lt, basis, k + r, a.out[r], pacc[r], lane);
   }
-  __syncthreads();
-  for (int s = wave; s < nsh; s += 4) {
-    uint32_t v = part[0][s] ^ part[1][s] ^ part[2][s] ^ part[3][s];
-    uint64_t e = t_begin < t_end ? a.ntiles - t_end : 0;
-    for (int b = 0; e; ++b, e >>= 1)
-      if (e & 1) v = mat_apply(lt.tile_pow2[b], v, lane);
-    if (lane == 0) a.part_crc[s * kMaxGridCrc + blockIdx.x] = v;
-  }
+  place_partials(a, lt, part, nsh, t_begin, t_end, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1982,6 +2188,57 @@ hipError_t launch_ec_fused(const EcFusedLaunch& a, const DevCrcTables* t, int gr
     case 7: hipLaunchKernelGGL((ec_fused_kernel<3, true>), g, b, 0, s, a, t); break;
     case 8: hipLaunchKernelGGL((ec_fused_kernel<4, false>), g, b, 0, s, a, t); break;
     default: hipLaunchKernelGGL((ec_fused_kernel<4, true>), g, b, 0, s, a, t); break;
+  }
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_ec_convert_fused{-1};
+
+void set_ec_convert_fused(bool on) { g_ec_convert_fused.store(on ? 1 : 0); }
+
+bool ec_convert_fused_enabled() {
+  int v = g_ec_convert_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_EC_CONVERT_FUSED");
+    g_ec_convert_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+int ec_convert_grid(uint64_t ntiles, uint32_t tail_len, int rows) {
+  // one resident round: two workgroups per CU, one from three accumulator rows up
+  const uint64_t cap = rows < 3 ? kEcFusedMaxGrid : kEcFusedMaxGrid / 2;
+  const uint64_t g = ntiles < cap ? ntiles : cap;
+  return static_cast<int>(g == 0 && tail_len ? 1 : g);
+}
+
+hipError_t launch_ec_convert(const EcConvertLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const EcFusedLaunch& f = a.f;
+  if (grid <= 0 || grid > kMaxGridCrc || f.k <= 0 || f.rows <= 0 || f.rows > kEcFusedMaxRows ||
+      f.k + f.rows > kMaxShards || a.n < 1 || a.sl != (a.n + f.k - 1) / f.k || !a.src || !f.tables || !f.part_crc ||
+      !f.tail_be)
+    return hipErrorInvalidValue;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(f.tables) |
+                   reinterpret_cast<uintptr_t>(f.part_crc) | reinterpret_cast<uintptr_t>(f.tail_be);
+  for (int c = 0; c < f.k; ++c) {
+    if (!f.dst[c]) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(f.dst[c]);
+  }
+  for (int r = 0; r < f.rows; ++r) {
+    if (!f.out[r]) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(f.out[r]);
+  }
+  for (int i = 0; i < f.k + f.rows; ++i) {
+    if (!f.meta[i]) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(f.meta[i]);
+  }
+  if (bits % 16) return hipErrorInvalidValue;
+  const dim3 g(grid), b(kCrcWgThreads);
+  switch (f.rows) {
+    case 1: hipLaunchKernelGGL((ec_convert_kernel<1>), g, b, 0, s, a, t); break;
+    case 2: hipLaunchKernelGGL((ec_convert_kernel<2>), g, b, 0, s, a, t); break;
+    case 3: hipLaunchKernelGGL((ec_convert_kernel<3>), g, b, 0, s, a, t); break;
+    default: hipLaunchKernelGGL((ec_convert_kernel<4>), g, b, 0, s, a, t); break;
   }
   return hipGetLastError();
 }

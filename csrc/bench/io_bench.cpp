@@ -31,6 +31,7 @@
 
 #include "trace.h"
 #include "chunk_store.h"
+#include "crypto.h"
 #include "disk_gate.h"
 #include "crc32.h"
 #include "gf256.h"
@@ -765,8 +766,101 @@ static int ec_read_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// --sse: ChunkStore::sse_crypt in place on a registered buffer whose body starts 12 bytes into a
+// 16 B vector (a slot's [nonce 12][body][tag 16]): the kernel path against OpenSSL on the calling
+// thread, alternating in every repetition, encrypt and decrypt. One JSON line per (size, direction)
+// cell; times are microseconds per call, each the mean of `iters` back-to-back calls, with the
+// median and the spread (max - min over the repetitions) of either path.
+static int sse_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--sse needs a GPU\n");
+    return 1;
+  }
+  std::filesystem::remove_all(dir);
+  StoreConfig cfg;
+  cfg.storage_dir = dir + "/sse";
+  cfg.device = device;
+  cfg.hbm_capacity = 256ull << 20;
+  ChunkStore s(cfg);
+  uint8_t key[32], nonce[12];
+  for (int i = 0; i < 32; ++i) key[i] = static_cast<uint8_t>(3 * i + 1);
+  for (int i = 0; i < 12; ++i) nonce[i] = static_cast<uint8_t>(7 * i + 5);
+  int rc = 0;
+  for (uint64_t n : {64ull << 10, 1ull << 20, 4ull << 20, 16ull << 20, 100ull << 20}) {
+    const auto plain = random_bytes(n, static_cast<uint32_t>(n + 29));
+    uint8_t* buf = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void**>(&buf), n + 64, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) return 1;
+    s.register_host(buf, n + 64);
+    uint8_t* body = buf + 12;
+    std::vector<uint8_t> sealed(plain);
+    uint8_t ref_tag[16];
+    crypto::aes256gcm_encrypt_inplace(key, nonce, sealed.data(), n, ref_tag);
+    for (int encrypt = 1; encrypt >= 0; --encrypt) {
+      const int iters = static_cast<int>(std::clamp<uint64_t>((64ull << 20) / n, 2, 100));
+      std::vector<double> us[2];  // [0] OpenSSL, [1] kernel
+      bool match = true;
+      auto run = [&](int fused, int count) {
+        set_sse_fused(fused != 0, 0);  // every size takes the kernel: the threshold is what this measures
+        double t = 0;
+        for (int i = 0; i < count && match; ++i) {
+          std::memcpy(body, encrypt ? plain.data() : sealed.data(), n);
+          uint8_t tag[16];
+          std::memcpy(tag, ref_tag, 16);
+          std::string err;
+          const auto t0 = Clock::now();
+          match = s.sse_crypt(body, n, key, nonce, encrypt != 0, tag, &err);
+          t += secs(t0, Clock::now());
+          match = match && std::memcmp(tag, ref_tag, 16) == 0 &&
+                  std::memcmp(body, encrypt ? sealed.data() : plain.data(), n) == 0;
+        }
+        return t * 1e6 / count;
+      };
+      for (int fused = 0; fused < 2; ++fused) run(fused, 2);  // warm-up: code object, scratch, OpenSSL's key setup
+      const uint64_t before = s.stats().sse_fused_crypts;
+      for (int rep = 0; rep < reps; ++rep)
+        for (int fused = 1; fused >= 0; --fused) us[fused].push_back(run(fused, iters));
+      match = match && s.stats().sse_fused_crypts - before == static_cast<uint64_t>(reps) * iters;
+      auto list = [](const std::vector<double>& v) {
+        std::string o;
+        for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+        return o;
+      };
+      auto median = [](std::vector<double> v) {
+        std::sort(v.begin(), v.end());
+        return v[v.size() / 2];
+      };
+      auto spread = [](const std::vector<double>& v) { return *std::max_element(v.begin(), v.end()) - *std::min_element(v.begin(), v.end()); };
+      std::printf("{\"sse\": {\"bytes\": %llu, \"encrypt\": %s, \"iters\": %d, \"kernel_us\": [%s], \"openssl_us\": [%s], "
+                  "\"kernel_median_us\": %.1f, \"openssl_median_us\": %.1f, \"kernel_spread_us\": %.1f, "
+                  "\"openssl_spread_us\": %.1f, \"kernel_gbps\": %.2f, \"openssl_gbps\": %.2f, \"match\": %s}}\n",
+                  static_cast<unsigned long long>(n), encrypt ? "true" : "false", iters, list(us[1]).c_str(),
+                  list(us[0]).c_str(), median(us[1]), median(us[0]), spread(us[1]), spread(us[0]), n / median(us[1]) / 1e3,
+                  n / median(us[0]) / 1e3, match ? "true" : "false");
+      std::fflush(stdout);
+      if (!match) rc = 1;
+    }
+    s.unregister_host(buf);
+    (void)hipHostFree(buf);
+  }
+  set_sse_fused(true, static_cast<int64_t>(kSseFusedMinBytes));
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 int main(int argc, char** argv) {
   dfs::trace_init();  // before any thread: roctx's first range calls setenv (trace.h)
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--sse") {
+      std::string dir = "/tmp/io_bench_sse";
+      int device = 0, reps = 5;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return sse_bench(device, dir, std::max(5, reps));
+    }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--ec-read") {
       std::string dir = "/tmp/io_bench_ecr";

@@ -246,6 +246,9 @@ PYBIND11_MODULE(_dfs_native, m) {
   m.def("set_ec_convert_fused", &set_ec_convert_fused,
         "EC conversion of a resident block in one kernel (else one copy per column, K4, K2 per shard)");
   m.def("set_ec_fused", &set_ec_fused, "device EC in one fused kernel per stripe (else copies, K4/K5, K2 per shard)");
+  m.def("set_sse_fused", &set_sse_fused, "SSE AES-256-GCM of registered bodies in one kernel (else OpenSSL)",
+        py::arg("on"), py::arg("min_bytes") = -1);
+  m.def("sse_fused_min_bytes", &sse_fused_min_bytes, "bodies below this many bytes stay on OpenSSL");
   m.def("set_ec_read_fused", &set_ec_read_fused, "degraded EC range reads in one kernel (else decode into HBM, then copies)");
   m.def("set_crc_wide", &set_crc_wide, "K1/K2 one workgroup per CU: 0 off, 1 shared LDS image, 2 + LDS basis");
   m.def("set_crc_kernels", [](bool mfma, int scrub_ring, int tile_ring) {
@@ -522,6 +525,25 @@ PYBIND11_MODULE(_dfs_native, m) {
         if (!ok) return py::none();
         return ec_result(s, &dec);
       }, py::arg("rows"), py::arg("block_ids"), py::arg("shard_len"))
+      // AES-256-GCM of SSE-S3 in place on a writable buffer (one kernel when the buffer is
+      // registered, OpenSSL otherwise); returns the tag, raises on an authentication failure.
+      .def("sse_crypt", [](ChunkStore& s, py::buffer buf, py::bytes key, py::bytes nonce, bool encrypt, py::bytes tag) {
+        py::buffer_info bi = buf.request(true);
+        std::string k = key, nc = nonce, t = tag, err;
+        if (k.size() != 32 || nc.size() != 12 || (!encrypt && t.size() != 16))
+          throw std::invalid_argument("sse_crypt: 32-byte key, 12-byte nonce and, to decrypt, the 16-byte tag");
+        t.resize(16);
+        bool ok;
+        {
+          py::gil_scoped_release rel;
+          ok = s.sse_crypt(static_cast<uint8_t*>(bi.ptr), static_cast<uint64_t>(bi.size * bi.itemsize),
+                           reinterpret_cast<const uint8_t*>(k.data()), reinterpret_cast<const uint8_t*>(nc.data()), encrypt,
+                           reinterpret_cast<uint8_t*>(&t[0]), &err);
+        }
+        gcm::wipe(&k[0], k.size());
+        if (!ok) throw std::runtime_error(err);
+        return py::bytes(t);
+      }, py::arg("buffer"), py::arg("key"), py::arg("nonce"), py::arg("encrypt"), py::arg("tag") = py::bytes())
       // degraded read: bytes [offset, offset + length) of the RS(k, m) file whose k + m shards are
       // the resident blocks `block_ids` ("" = lost) into `out`; a registered `out` takes the
       // single-kernel path. Returns the number of bytes placed, None on failure.
@@ -866,6 +888,18 @@ PYBIND11_MODULE(_dfs_native, m) {
     }
     return py::bytes(o);
   }, py::arg("key"), py::arg("nonce"), py::arg("ciphertext"), py::arg("aad") = py::bytes());
+  // GHASH_H(data || pad || length block) with H = E_key(0^128), through the SSE kernel's tile cut and
+  // the host fold of its workgroup partials (gcm_host.h); grid 0 = the kernel's grid for that size.
+  m.def("gcm_ghash", [](py::bytes key, py::bytes data, int grid) {
+    std::string k = key, d = data;
+    if (k.size() != 32) throw std::invalid_argument("gcm_ghash: 32-byte key");
+    uint8_t out[16];
+    const bool ok = gcm::ghash(reinterpret_cast<const uint8_t*>(k.data()), reinterpret_cast<const uint8_t*>(d.data()), d.size(), grid, out);
+    gcm::wipe(&k[0], k.size());
+    if (!ok)
+      throw std::runtime_error("gcm_ghash: AES block encryption failed");
+    return py::bytes(reinterpret_cast<const char*>(out), 16);
+  }, py::arg("key"), py::arg("data"), py::arg("grid") = 0);
   m.def("rsa_sha256_verify", [](py::bytes n, py::bytes e, py::bytes msg, py::bytes sig) {
     return crypto::rsa_sha256_verify(n, e, msg, sig);
   });

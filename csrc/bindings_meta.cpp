@@ -26,6 +26,7 @@
 #include "grpc_server.h"
 #include "localrpc.h"
 #include "config_core.h"
+#include "gcm_host.h"
 #include "master_core.h"
 #include "raft.h"
 #include "s3_front.h"
@@ -997,6 +998,7 @@ void bind_meta(py::module_& m) {
         d["tls_failures"] = s.tls_failures;
         d["sse_puts"] = s.sse_puts;
         d["sse_gets"] = s.sse_gets;
+        d["sse_offloaded"] = s.sse_offloaded;
         d["iam_native"] = s.iam_native;
         d["lists"] = s.lists;
         d["mpu_completes"] = s.mpu_completes;
@@ -1118,6 +1120,25 @@ void bind_meta(py::module_& m) {
         }
         return py::make_tuple(static_cast<int>(st), msg);
       }, py::arg("path"), py::arg("data"), py::arg("k"), py::arg("m"), py::arg("request_id") = "")
+      // AES-256-GCM in place over arena bytes [off, off + n) on the chunkserver's GPU (op 10):
+      // (status, tag); status 0 done, 1 not handled (nothing touched), 2 authentication failure
+      .def("sse_crypt", [](FastClient& c, uint64_t off, uint64_t n, py::bytes key, py::bytes nonce, bool encrypt,
+                           py::bytes tag, const std::string& rid) {
+        std::string k = key, nc = nonce, t = tag;
+        if (k.size() != 32 || nc.size() != 12 || (!encrypt && t.size() != 16))
+          throw std::invalid_argument("sse_crypt: 32-byte key, 12-byte nonce and, to decrypt, the 16-byte tag");
+        t.resize(16);
+        FastClient::Status st;
+        {
+          py::gil_scoped_release r;
+          st = c.sse_crypt(off, n, reinterpret_cast<const uint8_t*>(k.data()), reinterpret_cast<const uint8_t*>(nc.data()),
+                           encrypt, reinterpret_cast<uint8_t*>(&t[0]), rid);
+        }
+        gcm::wipe(&k[0], k.size());
+        return py::make_tuple(static_cast<int>(st), py::bytes(t));
+      }, py::arg("off"), py::arg("n"), py::arg("key"), py::arg("nonce"), py::arg("encrypt"), py::arg("tag") = py::bytes(),
+         py::arg("request_id") = "")
+      .def_property_readonly("sse_gpu_ops", &FastClient::sse_gpu_ops)
       .def_property_readonly("ec_gpu_ops", &FastClient::ec_gpu_ops)
       .def_property_readonly("ec_cpu_ops", &FastClient::ec_cpu_ops)
       .def_property_readonly("ec_degraded_reads", &FastClient::ec_degraded_reads)

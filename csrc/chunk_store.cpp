@@ -21,7 +21,11 @@
 #include <stdexcept>
 #include <unordered_map>
 
+#include <openssl/crypto.h>
+
 #include "crc32.h"
+#include "crypto.h"
+#include "gcm_host.h"
 #include "gf256.h"
 
 namespace dfs {
@@ -2558,6 +2562,7 @@ StoreStats ChunkStore::stats() {
   s.ec_fused_converts = ec_fused_converts_.load();
   s.ec_fused_decodes = ec_fused_decodes_.load();
   s.ec_fused_reads = ec_fused_reads_.load();
+  s.sse_fused_crypts = sse_fused_crypts_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -4077,6 +4082,77 @@ ChunkStore::EcRead ChunkStore::ec_read_range(const std::vector<const uint8_t*>& 
   }
   ec_free(&dec);
   return ok ? EcRead::Ok : EcRead::CopyFailed;
+}
+
+bool ChunkStore::sse_fusable(const uint8_t* p, uint64_t n) {
+  return gpu() && sse_fused_enabled() && n >= std::max<uint64_t>(1, sse_fused_min_bytes()) &&
+         gcm::plan_for(n).nblocks <= 0xFFFFFFFEull && reinterpret_cast<uintptr_t>(p) % 4 == 0 &&
+         device_view(p, n) != nullptr;
+}
+
+bool ChunkStore::sse_crypt(uint8_t* p, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt,
+                           uint8_t tag[16], std::string* err) {
+  TraceRange tr("dfs.store.sse_crypt");  // no key material in ranges, logs or errors
+  uint8_t* dev = sse_fusable(p, n) ? device_view(p, n) : nullptr;
+  if (dev) {
+    HIP_OK(hipSetDevice(cfg_.device));
+    const gcm::Plan plan = gcm::plan_for(n);
+    Lane* l = acquire_lane();
+    ensure_hscratch(l, plan.grid * sizeof(gcm::U128));
+    // Nothing below throws: the lane is released and every copy of the key schedule and the powers
+    // of H that the store owns is wiped on each way out. A launch that fails has written nothing,
+    // so the call goes on to OpenSSL; a failed synchronise has, and is an error.
+    gcm::Keys keys;
+    SseGcmLaunch a{};
+    hipError_t launched = hipErrorNotReady, synced = hipSuccess;
+    uint8_t got[16] = {0};
+    if (l->hscratch_dev && gcm::prepare(key, nonce, plan, &keys)) {
+      a.src = a.dst = dev;
+      a.n = n;
+      a.ntiles = plan.ntiles;
+      a.vfront = plan.vfront;
+      a.encrypt = encrypt ? 1 : 0;
+      std::memcpy(a.nonce, keys.nonce, sizeof(a.nonce));
+      std::memcpy(a.rk, keys.rk, sizeof(a.rk));
+      a.h = keys.h;
+      a.hjump = keys.hjump;
+      std::memcpy(a.tree, keys.tree, sizeof(a.tree));
+      a.part = static_cast<gcm::U128*>(l->hscratch_dev);
+      launched = launch_sse_gcm(a, dtables_, plan.grid, l->stream);
+      if (launched == hipSuccess) {
+        launches_++;
+        synced = hipStreamSynchronize(l->stream);
+        if (synced == hipSuccess)
+          gcm::finish_tag(keys, gcm::ghash_fold(keys, plan, reinterpret_cast<const gcm::U128*>(l->hscratch)), n, got);
+        gcm::wipe(l->hscratch, plan.grid * sizeof(gcm::U128));
+      }
+    }
+    gcm::wipe(&a, sizeof(a));
+    gcm::wipe(&keys, sizeof(keys));
+    release_lane(l);
+    if (launched == hipSuccess) {
+      if (synced != hipSuccess) {
+        *err = std::string("SSE kernel: ") + hipGetErrorString(synced);
+        return false;
+      }
+      sse_fused_crypts_++;
+      if (encrypt) {
+        std::memcpy(tag, got, 16);
+        return true;
+      }
+      if (CRYPTO_memcmp(got, tag, 16) == 0) return true;
+      *err = kSseAuthFailed;
+      return false;
+    }
+    (void)hipGetLastError();
+  }
+  if (encrypt) {
+    crypto::aes256gcm_encrypt_inplace(key, nonce, p, n, tag);
+    return true;
+  }
+  if (crypto::aes256gcm_decrypt_inplace(key, nonce, p, n, tag)) return true;
+  *err = kSseAuthFailed;
+  return false;
 }
 
 bool ChunkStore::device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n) {

@@ -95,6 +95,7 @@ struct StoreStats {
   uint64_t ec_fused_converts = 0;  // resident blocks turned into RS shards by one ec_convert_kernel launch
   uint64_t ec_fused_decodes = 0;  // shard sets rebuilt and checksummed by one ec_fused_kernel launch
   uint64_t ec_fused_reads = 0;    // degraded EC range reads served by one ec_read_kernel launch
+  uint64_t sse_fused_crypts = 0;  // SSE bodies encrypted or decrypted by one sse_gcm_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -313,6 +314,16 @@ class ChunkStore {
   enum class EcRead { Ok, DecodeFailed, CopyFailed };
   EcRead ec_read_range(const std::vector<const uint8_t*>& shards, int k, int m, uint64_t sl, uint64_t from,
                        uint64_t want, uint8_t* dst, std::string* err);
+  // AES-256-GCM of SSE-S3 in place: p[0, n) with the object's data key and its 96-bit nonce, no
+  // AAD. Encrypt writes `tag`; decrypt compares it in constant time and returns false, with *err
+  // set, when it does not match. Registered `p` with p % 4 == 0 and n >= sse_fused_min_bytes() on a
+  // GPU store: one sse_gcm_kernel launch over the bytes where they lie, the tag folded on the host.
+  // Otherwise OpenSSL on the calling thread; the bytes are the same either way. The key schedule
+  // and the powers of H are wiped before this returns.
+  static constexpr const char* kSseAuthFailed = "aead::Error: authentication failed";
+  bool sse_fusable(const uint8_t* p, uint64_t n);  // would sse_crypt take the kernel for p[0, n)
+  bool sse_crypt(uint8_t* p, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt, uint8_t tag[16],
+                 std::string* err);
   // Device bytes into host memory (registered: one DMA) and synchronously complete.
   bool device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n);
   // A copy of device bytes committed as block `id` (checksummed, verified, made durable).
@@ -515,7 +526,8 @@ class ChunkStore {
   // block of n bytes.
   bool ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
                 std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
-  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0};
+  std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0},
+      sse_fused_crypts_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

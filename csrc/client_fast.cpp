@@ -1,4 +1,5 @@
 #include "client_fast.h"
+#include "gcm_host.h"
 #include "gf256.h"
 #include "trace.h"
 
@@ -775,6 +776,32 @@ bool FastClient::ec_matmul(const std::vector<std::vector<uint8_t>>& mat, int k, 
   gf::matmul_cpu(mat, in.data(), out.data(), len);
   ec_cpu_++;
   return true;
+}
+
+FastClient::Status FastClient::sse_crypt(uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12],
+                                         bool encrypt, uint8_t tag[16], const std::string& rid) {
+  if (!base_ || n == 0) return NotHandled;
+  std::string body;
+  put<uint8_t>(body, encrypt ? 1 : 0);
+  put<uint64_t>(body, off);
+  put<uint64_t>(body, n);
+  put_str(body, std::string(reinterpret_cast<const char*>(key), 32));
+  put_str(body, std::string(reinterpret_cast<const char*>(nonce), 12));
+  put_str(body, encrypt ? std::string() : std::string(reinterpret_cast<const char*>(tag), 16));
+  put_str(body, arena_path_);
+  put_str(body, rid);
+  uint8_t st = 0;
+  uint64_t total = 0, got = 0;
+  std::string hex;
+  const bool sent = fp_call(10, body, &st, &total, &got, &hex);
+  gcm::wipe(&body[0], body.size());
+  if (!sent) return NotHandled;
+  if (st == 9) return Failed;  // FpStatus::AuthFailed
+  if (st != 0 || hex.size() != 32) return NotHandled;
+  auto nib = [](char ch) { return ch <= '9' ? ch - '0' : ch - 'a' + 10; };
+  for (int i = 0; i < 16; ++i) tag[i] = static_cast<uint8_t>(nib(hex[2 * i]) << 4 | nib(hex[2 * i + 1]));
+  sse_gpu_++;
+  return Ok;
 }
 
 FastClient::Status FastClient::write_ec(const std::string& path, const uint8_t* data, size_t n, int k, int m,

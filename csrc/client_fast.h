@@ -126,6 +126,14 @@ class FastClient {
   // and decode the missing data shards on the GPU from the layout as fetched.
   Status write_ec(const std::string& path, const uint8_t* data, size_t n, int k, int m, std::string* msg,
                   const std::string& rid);
+  // AES-256-GCM of SSE-S3 in place over slot bytes [off, off + n) on the co-located chunkserver's
+  // GPU (fast-path op 10). Ok: done, `tag` written (encrypt) or verified (decrypt). Failed: the tag
+  // does not match, which is final. NotHandled: nothing was touched (no GPU, slot not pinned, body
+  // below the kernel's floor, transport error) and the caller encrypts on its own CPU. The data key
+  // crosses only the peer-credential-checked abstract socket on this host.
+  Status sse_crypt(uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt,
+                   uint8_t tag[16], const std::string& rid);
+  uint64_t sse_gpu_ops() const { return sse_gpu_.load(); }
   uint64_t ec_gpu_ops() const { return ec_gpu_.load(); }
   uint64_t ec_cpu_ops() const { return ec_cpu_.load(); }
   uint64_t ec_degraded_reads() const { return ec_degraded_.load(); }
@@ -204,7 +212,7 @@ class FastClient {
     return !md5mb_ ? "openssl" : md5mb_->kind() == Md5MultiBuffer::Kind::Avx512 ? "avx512-x16" : md5mb_->lanes() == 3 ? "scalar-x3" : md5mb_->lanes() == 2 ? "scalar-x2" : "scalar-x1";
   }
 
-  std::atomic<uint64_t> writes_{0}, reads_{0}, ec_gpu_{0}, ec_cpu_{0}, ec_degraded_{0};
+  std::atomic<uint64_t> writes_{0}, reads_{0}, ec_gpu_{0}, ec_cpu_{0}, ec_degraded_{0}, sse_gpu_{0};
   std::atomic<uint64_t> ec_dev_writes_{0}, ec_dev_reads_{0}, ec_host_{0};
   GrpcChannelPool grpc_{120000};  // shard I/O with servers on other hosts
   IoPool shard_pool_{8};         // last: destroyed first, after in-flight shard I/O

@@ -930,6 +930,49 @@ void FastPathServer::serve(int fd) {
         sent = ok ? send_response(fd, FpStatus::Ok, len, rows, "")
                   : send_response(fd, FpStatus::Unsupported, 0, 0, "GPU erasure coding failed");
       }
+    } else if (op == 10) {  // SSE_CRYPT: AES-256-GCM over the body in the client's slot, on this GPU
+      const uint8_t encrypt = rd.get<uint8_t>();
+      const uint64_t off = rd.get<uint64_t>(), len = rd.get<uint64_t>();
+      std::string key = rd.str(), nonce = rd.str(), tag = rd.str(), path = rd.str();
+      std::string rid = rd.p < rd.end ? rd.str() : std::string();
+      RequestScope rs(rid);
+      note_rid(rid);
+      TraceRange tr("dfs.fp.sse");  // the key stays out of ranges, logs and answers
+      std::string err;
+      uint8_t* base = nullptr;
+      // bounded like op 6: the offset before any pointer is formed, the length by map_shm
+      if (!rd.ok || encrypt > 1 || key.size() != 32 || nonce.size() != 12 || tag.size() != (encrypt ? 0u : 16u) ||
+          len == 0 || len > kMaxTransfer || off > (1ull << 62)) {
+        sent = send_response(fd, FpStatus::BadRequest, 0, 0, "malformed sse request");
+      } else if (!store_->gpu()) {
+        sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU on this chunkserver");
+      } else if ((base = map_shm(path, off, len, &err)) == nullptr) {
+        sent = send_response(fd, FpStatus::Unsupported, 0, 0, "short-circuit unavailable: " + err);
+      } else {
+        {  // a new arena is pinned off this thread: the first body waits for that instead of losing the GPU
+          std::unique_lock<std::mutex> lk(mu_);
+          workers_cv_.wait(lk, [this] { return pending_regs_ == 0; });
+        }
+        tag.resize(16);
+        if (!store_->sse_fusable(base + off, len)) {
+          sent = send_response(fd, FpStatus::Unsupported, 0, 0, "slot not pinned or body below the kernel's floor");
+        } else if (store_->sse_crypt(base + off, len, reinterpret_cast<const uint8_t*>(key.data()),
+                                     reinterpret_cast<const uint8_t*>(nonce.data()), encrypt != 0,
+                                     reinterpret_cast<uint8_t*>(&tag[0]), &err)) {
+          static const char* hx = "0123456789abcdef";
+          std::string hex;
+          for (unsigned char ch : tag) {
+            hex.push_back(hx[ch >> 4]);
+            hex.push_back(hx[ch & 15]);
+          }
+          bump(&FpStats::sse_crypts);
+          sent = send_response(fd, FpStatus::Ok, len, len, hex);
+        } else {
+          sent = send_response(fd, FpStatus::AuthFailed, 0, 0, err);
+        }
+      }
+      gcm::wipe(&key[0], key.size());
+      gcm::wipe(body.data(), body.size());
     } else if (op == 7) {  // EC_WRITE: encode in HBM, scatter the shards over the engine
       sent = ec_write(fd, body.data() + 1, body.data() + n);
     } else if (op == 8) {  // EC_READ: gather the surviving shards into HBM, decode there

@@ -36,6 +36,11 @@
 //               there, the requested range DMA'd into the client's slot
 //     op 9 PUSH: u16 id | u16 as_id | u16 dst_addr [| u16 rid] -- send local block `id` to the
 //               same-node peer `dst_addr` over the engine, stored there as ephemeral `as_id`
+//     op 10 SSE_CRYPT: u8 encrypt | u64 shm_off | u64 len | u16 key(32) | u16 nonce(12) | u16 tag(16, or
+//               empty to encrypt) | u16 path [| u16 rid]  -- AES-256-GCM of SSE-S3 in place over the body in
+//               the client's slot, by sse_gcm_kernel; answers Ok with the tag as 32 hex digits in msg,
+//               AuthFailed, or Unsupported when the kernel would not take it (no GPU, slot not pinned,
+//               below the store's floor): the client then encrypts on its own CPU
 //   response = u32 body_len | u8 status | u64 total | u64 bytes | u16 msg_len msg
 //   (for WRITE/REPL ``bytes`` carries replicas_written; for CTRL ``msg`` is the engine reply)
 //
@@ -73,6 +78,7 @@ enum class FpStatus : uint8_t {
   Unsupported = 6,  // use gRPC
   BadRequest = 7,
   PartialCorrupt = 8,  // data returned; block queued for background recovery
+  AuthFailed = 9,      // SSE_CRYPT: the tag does not match (final: no path will decrypt these bytes)
 };
 
 struct FpStats {
@@ -82,6 +88,7 @@ struct FpStats {
   uint64_t replica_failures = 0;  // replicas that could not be written (not counted)
   uint64_t p2p_fallbacks = 0;     // replicas moved to shared memory after a P2P failure
   uint64_t ec_ops = 0;            // erasure-coding matrix products run for clients
+  uint64_t sse_crypts = 0;        // SSE bodies encrypted or decrypted in clients' slots
   uint64_t heals_out = 0, heals_in = 0;  // heal / balancer copies sent / received on the engine
   uint64_t sliced_writes = 0;  // head writes whose replica sends overlapped the staging
   // device-resident erasure coding: EC writes whose shards were encoded and scattered HBM ->

@@ -67,6 +67,13 @@ class FrontStore {
     }
     return FastClient::Ok;
   }
+  // AES-256-GCM of SSE-S3 in place over slot bytes [off, off + n) somewhere other than this
+  // thread (FastClient::sse_crypt). NotHandled, the default: the caller does it itself.
+  virtual Status sse_crypt(int64_t slot, uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12],
+                           bool encrypt, uint8_t tag[16], const std::string& rid) {
+    (void)slot, (void)off, (void)n, (void)key, (void)nonce, (void)encrypt, (void)tag, (void)rid;
+    return FastClient::NotHandled;
+  }
   // calls a first-choice path declined and a second one served (LocalFirstFrontStore)
   virtual uint64_t fallbacks() const { return 0; }
 };
@@ -105,6 +112,10 @@ class FastFrontStore final : public FrontStore {
   }
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid) override {
     return fc_->list_components(prefix, out, rid);
+  }
+  Status sse_crypt(int64_t slot, uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt,
+                   uint8_t tag[16], const std::string& rid) override {
+    return slot < 0 ? FastClient::NotHandled : fc_->sse_crypt(static_cast<uint64_t>(slot) + off, n, key, nonce, encrypt, tag, rid);
   }
 
  private:
@@ -179,6 +190,10 @@ class LocalFirstFrontStore final : public FrontStore {
   Status list(const std::string& prefix, std::vector<std::pair<std::string, pb::FileMetadata>>* out,
               const std::string& rid) override;
   uint64_t fallbacks() const override { return fallbacks_.load(); }
+  Status sse_crypt(int64_t slot, uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt,
+                   uint8_t tag[16], const std::string& rid) override {
+    return slot < 0 ? FastClient::NotHandled : fc_->sse_crypt(static_cast<uint64_t>(slot) + off, n, key, nonce, encrypt, tag, rid);
+  }
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid) override {
     if (fc_->list_components(prefix, out, rid) == FastClient::Ok) return FastClient::Ok;
     ++fallbacks_;

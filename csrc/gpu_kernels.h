@@ -14,10 +14,15 @@
 //   K5 + range read  ec_read_kernel: a byte range of an RS-coded file whose data shards are partly
 //          lost — only the lost columns inside the range are rebuilt, and the bytes go from the
 //          registers over PCIe into the reader's registered buffer.
+//   K7     sse_gcm_kernel: the AES-256-GCM of SSE-S3 over a body in registered host memory — CTR
+//          keystream from a T-table in LDS, XOR in place, and the GHASH of the ciphertext as
+//          per-workgroup partials that the host folds into the tag.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "gcm_host.h"
 
 namespace dfs {
 
@@ -32,6 +37,9 @@ constexpr int kCrcWideExtraBytes = 8 * 4 * 256 * 4;
 // behind those: the basis of the FP4 matrix-core form (8 A fragments of 16 B per lane)
 constexpr int kCrcBasisFp4Bytes = 8 * 64 * 16;
 constexpr int kCrcBasisFp4Offset = kCrcBasisBytes + kCrcChunkShiftBytes + kCrcWideExtraBytes;  // after DevCrcTables
+// behind those: the AES tables of sse_gcm_kernel (Te0, 256 words, then the S-box, 256 bytes)
+constexpr int kSseTablesOffset = kCrcBasisFp4Offset + kCrcBasisFp4Bytes;
+constexpr int kSseTablesBytes = 256 * 4 + 256;
 
 struct DevCrcTables {
   uint32_t slice16[16][256];
@@ -242,6 +250,36 @@ struct EcReadLaunch {
 bool ec_read_fused_enabled();
 void set_ec_read_fused(bool on);
 hipError_t launch_ec_read(const EcReadLaunch& a, hipStream_t s);
+
+// K7, AES-256-GCM of one message of n >= 1 bytes, no AAD (sse_gcm_kernel): dst = src XOR keystream
+// and the GHASH of the ciphertext (dst when encrypting, src when decrypting) as one 128-bit partial
+// per workgroup in `part`, which gcm::ghash_fold and gcm::finish_tag turn into the tag. `src` and
+// `dst` are device views of registered host memory with src % 4 == 0 and (dst - src) % 16 == 0, equal
+// (in place) or disjoint; only [dst, dst + n) is written, though the 16 B vectors that hold the
+// message's first and last bytes are read whole. The plan is gcm::plan_for(n), the key schedule and
+// the powers of H come from gcm::prepare for that plan, and `grid` is the plan's. The key material
+// travels as kernel arguments (scalar registers), never through memory the store owns.
+struct SseGcmLaunch {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t n, ntiles, vfront;
+  uint32_t encrypt;
+  uint32_t nonce[3];
+  uint32_t rk[60];
+  gcm::U128 h, hjump, tree[gcm::kGcmTreeSteps];
+  gcm::U128* part;  // device-visible: [grid]
+};
+// DFS_SSE_FUSED=0 keeps OpenSSL on the calling thread. Bodies below sse_fused_min_bytes() stay there
+// too: a call costs ~120 us before the first byte (key schedule and powers of H on the host, launch,
+// synchronise, and a GHASH tree of 128-step multiplies per workgroup), which OpenSSL at 6.6 GB/s
+// undercuts at 64 KiB (10 us) and at 1 MiB (155 against 162 us); 4 MiB is the smallest measured size
+// the kernel wins (274 against 621 us, profiles/r10). DFS_SSE_FUSED_MIN_BYTES overrides; set_sse_fused is the benches' and tests' switch
+// (min_bytes < 0 keeps the threshold).
+constexpr uint64_t kSseFusedMinBytes = 4ull << 20;
+bool sse_fused_enabled();
+uint64_t sse_fused_min_bytes();
+void set_sse_fused(bool on, int64_t min_bytes = -1);
+hipError_t launch_sse_gcm(const SseGcmLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

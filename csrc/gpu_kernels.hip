@@ -1830,6 +1830,187 @@ __global__ __launch_bounds__(kCrcWgThreads) void ec_read_kernel(EcReadLaunch a) 
   }
 }
 
+// ---- K7: AES-256-GCM of a body in registered host memory (SSE-S3) ----
+//
+// Work split. The tile axis is the message's 16 B block axis, right-aligned (gcm_host.h): tile T,
+// thread t owns blocks T * 1024 + 4t - vfront .. + 3, and a block below 0 does not exist. Workgroups
+// stride over tiles; the next tile's vectors are loaded before the current one is encrypted.
+//
+// Alignment. The message starts Q dwords into a 16 B vector (Q = (src & 15) / 4, a template
+// argument, so every funnel below indexes registers statically). All global traffic is on the
+// aligned vector grid: a thread loads its four vectors, takes the Q dwords that its last block
+// still lacks from the thread above (lane 63 loads that one vector itself), and after the XOR
+// hands its last Q dwords up the same way, so that vectors leave whole. Only a wave's first vector
+// (its low Q dwords belong to the wave below, which stores them) and the vectors holding the
+// message's first and last bytes leave as dwords or bytes: nothing outside [dst, dst + n) is
+// written. In place is safe because no thread uses bytes that another one writes: lane 63's load of
+// the vector above does overlap dwords Q..3 of it, which the next wave's lane 0 stores, but it uses
+// only dwords 0..Q-1, which it alone writes, and lane 0 in turn ignores those.
+//
+// AES. Te0 (1 KiB) and the S-box (256 B) sit in LDS; the other three tables are rotates. Four
+// blocks go through each round together. The round keys are kernel arguments: scalar loads.
+//
+// GHASH. A thread keeps one accumulator for all its tiles: (acc ^ C) * H per block, and
+// * H^(1024 * grid - 4) between its tiles, so every block costs one multiply. After the last tile
+// the accumulators combine in a log tree with H^(4 * 2^s) (shuffles inside a wave, LDS across the
+// four waves) into the workgroup's partial. Multiplies are shift-and-XOR in VGPRs with the
+// wave-uniform power of H as the operand whose bits are tested.
+__device__ __forceinline__ gcm::U128 shuffle_down(const gcm::U128& v, int by) {
+  const uint32_t a = __shfl_down(static_cast<uint32_t>(v.hi >> 32), by), b = __shfl_down(static_cast<uint32_t>(v.hi), by),
+                 c = __shfl_down(static_cast<uint32_t>(v.lo >> 32), by), d = __shfl_down(static_cast<uint32_t>(v.lo), by);
+  return gcm::U128{static_cast<uint64_t>(a) << 32 | b, static_cast<uint64_t>(c) << 32 | d};
+}
+
+// Dwords [lo, hi) of the 16 B vector whose first byte is message byte `pos` (pos % 4 == 0, may
+// be negative), clipped to the message [0, n).
+__device__ __forceinline__ void sse_store(uint8_t* dst, int64_t pos, int64_t n, const uint32_t (&w)[4], int lo,
+                                          int hi) {
+  if (lo == 0 && hi == 4 && pos >= 0 && pos + 16 <= n) {
+    *reinterpret_cast<uint4*>(dst + pos) = make_uint4(w[0], w[1], w[2], w[3]);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t p = pos + 4 * k;
+    if (k < lo || k >= hi || p < 0 || p >= n) continue;
+    if (p + 4 <= n) {
+      *reinterpret_cast<uint32_t*>(dst + p) = w[k];
+    } else {
+      for (int i = 0; p + i < n; ++i) dst[p + i] = static_cast<uint8_t>(w[k] >> (8 * i));
+    }
+  }
+}
+
+template <int Q>
+__global__ __launch_bounds__(kCrcWgThreads) void sse_gcm_kernel(SseGcmLaunch a, const DevCrcTables* __restrict__ gt) {
+  static_assert(Q >= 0 && Q < 4 && kCrcWgThreads == 256 && gcm::kGcmTileBlocks == 4 * kCrcWgThreads, "tile shape");
+  __shared__ uint32_t te0[256];
+  __shared__ uint8_t sbox[256];
+  __shared__ gcm::U128 wave_part[4];
+  {
+    const uint8_t* img = reinterpret_cast<const uint8_t*>(gt) + sizeof(DevCrcTables) + kSseTablesOffset;
+    te0[threadIdx.x] = reinterpret_cast<const uint32_t*>(img)[threadIdx.x];
+    sbox[threadIdx.x] = img[1024 + threadIdx.x];
+  }
+  __syncthreads();
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n = static_cast<int64_t>(a.n), nvec = (n + 4 * Q + 15) / 16;
+  // vector v of the aligned grid holds message bytes [16v - 4Q, 16v - 4Q + 16)
+  const u32x4* src = reinterpret_cast<const u32x4*>(a.src - 4 * Q);  // may alias dst: no __restrict__
+  uint8_t* dst = a.dst;
+  auto first_block = [&](uint64_t tile) {
+    return static_cast<int64_t>(tile * gcm::kGcmTileBlocks + 4 * threadIdx.x) - static_cast<int64_t>(a.vfront);
+  };
+  auto load = [&](int64_t v) {
+    uint4 d = make_uint4(0, 0, 0, 0);
+    if (v >= 0 && v < nvec) {
+      const u32x4 x = __builtin_nontemporal_load(src + v);
+      d = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    return d;
+  };
+  // a thread's four vectors and, in lane 63, the one above them
+  auto fetch = [&](uint64_t tile, uint4 (&v)[4], uint4& above) {
+    const int64_t j0 = first_block(tile);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = load(j0 + i);
+    above = Q > 0 && lane == 63 ? load(j0 + 4) : make_uint4(0, 0, 0, 0);
+  };
+
+  gcm::U128 acc{0, 0};
+  uint4 cur[4], cur_above;
+  fetch(blockIdx.x, cur, cur_above);
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    uint4 nxt[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+    uint4 nxt_above = make_uint4(0, 0, 0, 0);
+    if (tile + gridDim.x < a.ntiles) fetch(tile + gridDim.x, nxt, nxt_above);
+    const int64_t j0 = first_block(tile);
+
+    // the message dwords of the thread's four blocks: own dwords from Q on, then Q from above
+    const uint32_t d[16] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                            cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+    const uint32_t ab[4] = {cur_above.x, cur_above.y, cur_above.z, cur_above.w};
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i + Q < 16) {
+        m[i] = d[i + Q];
+      } else {
+        const uint32_t up = __shfl_down(d[i + Q - 16], 1);
+        m[i] = lane == 63 ? ab[i + Q - 16] : up;
+      }
+    }
+
+    uint32_t ks[4][4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      ks[b][0] = a.nonce[0];
+      ks[b][1] = a.nonce[1];
+      ks[b][2] = a.nonce[2];
+      ks[b][3] = gcm::bswap32(2u + static_cast<uint32_t>(j0 + b));
+    }
+    gcm::aes256_encrypt_words<4>(te0, sbox, a.rk, ks);
+
+    uint32_t o[16];
+    if (tile != blockIdx.x) acc = gcm::gf128_mul(a.hjump, acc);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      uint32_t c[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        o[4 * b + k] = m[4 * b + k] ^ ks[b][k];
+        // the ciphertext, zero where the block lies outside the message (its short end included)
+        const int64_t left = j0 + b < 0 ? 0 : n - 16 * (j0 + b) - 4 * k;
+        const uint32_t keep = left >= 4 ? ~0u : left <= 0 ? 0u : (1u << (8 * left)) - 1u;
+        c[k] = (a.encrypt ? o[4 * b + k] : m[4 * b + k]) & keep;
+      }
+      const gcm::U128 e = gcm::ghash_element(c[0], c[1], c[2], c[3]);
+      acc = gcm::gf128_mul(a.h, gcm::U128{acc.hi ^ e.hi, acc.lo ^ e.lo});
+    }
+
+    // back onto the vector grid: vector j0 + i takes dwords [4i - Q, 4i - Q + 4) of the output,
+    // the first Q of them from the thread below
+    uint32_t below[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < Q; ++i) below[i] = __shfl_up(o[16 - Q + i], 1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      uint32_t w[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = 4 * i + k < Q ? below[(4 * i + k) & 3] : o[(4 * i + k - Q) & 15];
+      sse_store(dst, 16 * (j0 + i) - 4 * Q, n, w, i == 0 && lane == 0 ? Q : 0, 4);
+    }
+    if (Q > 0 && lane == 63) {  // the low Q dwords of the vector above the wave's span
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < Q; ++k) w[k] = o[16 - Q + k];
+      sse_store(dst, 16 * (j0 + 4) - 4 * Q, n, w, 0, Q);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+    cur_above = nxt_above;
+  }
+
+  // a thread's accumulator stands at the end of its four blocks in the workgroup's last tile
+#pragma unroll 1
+  for (int s = 0; s < 6; ++s) {
+    const gcm::U128 right = shuffle_down(acc, 1 << s), left = gcm::gf128_mul(a.tree[s], acc);
+    acc = gcm::U128{left.hi ^ right.hi, left.lo ^ right.lo};
+  }
+  if (lane == 0) wave_part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    gcm::U128 y = wave_part[0];
+#pragma unroll 1
+    for (int w = 1; w < 4; ++w) {
+      y = gcm::gf128_mul(a.tree[6], y);
+      y = gcm::U128{y.hi ^ wave_part[w].hi, y.lo ^ wave_part[w].lo};
+    }
+    a.part[blockIdx.x] = y;
+  }
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -1964,7 +2145,9 @@ DevCrcTables* upload_crc_tables(hipStream_t s) {
   // MFMA basis right behind the LDS image (never copied to LDS): fragment [s][lane] of A,
   // element j = byte j of the 16 B: CRC bit i = lane & 31 of V[32h + 4(s>>1) + (j&3)][4(s&1) + (j>>2)],
   // scaled by 2^(7-p) (see wave_chunk_crcs)
-  host.resize(sizeof(DevCrcTables) + kCrcBasisFp4Offset + kCrcBasisFp4Bytes);
+  host.resize(sizeof(DevCrcTables) + kSseTablesOffset + kSseTablesBytes);
+  static_assert(sizeof(gcm::AesTables) == kSseTablesBytes && kSseTablesOffset % 16 == 0, "AES tables end the image");
+  std::memcpy(host.data() + sizeof(DevCrcTables) + kSseTablesOffset, &gcm::aes_tables(), kSseTablesBytes);
   static_assert(kCrcBasisFp4Offset == kCrcBasisBytes + kCrcChunkShiftBytes + kCrcWideExtraBytes, "image order");
   // chunk-shift tables behind the basis: cs[sl] moves a 64 B chunk's CRC past 64 * (7 - sl) bytes;
   // then ss[sw] (a slice's CRC past 512 * (7 - sw) bytes) and the 16 KiB tile shift
@@ -2292,6 +2475,50 @@ hipError_t launch_ec_read(const EcReadLaunch& in, hipStream_t s) {
     case 2: hipLaunchKernelGGL(ec_read_kernel<2>, g, b, 0, s, a); break;
     case 3: hipLaunchKernelGGL(ec_read_kernel<3>, g, b, 0, s, a); break;
     default: hipLaunchKernelGGL(ec_read_kernel<4>, g, b, 0, s, a); break;
+  }
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_sse_fused{-1};
+
+static std::atomic<int64_t> g_sse_min_bytes{-1};
+
+void set_sse_fused(bool on, int64_t min_bytes) {
+  g_sse_fused.store(on ? 1 : 0);
+  if (min_bytes >= 0) g_sse_min_bytes.store(min_bytes);
+}
+
+uint64_t sse_fused_min_bytes() {
+  int64_t v = g_sse_min_bytes.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_FUSED_MIN_BYTES");
+    g_sse_min_bytes.store(v = e && std::atoll(e) >= 0 ? std::atoll(e) : static_cast<int64_t>(kSseFusedMinBytes));
+  }
+  return static_cast<uint64_t>(v);
+}
+
+bool sse_fused_enabled() {
+  int v = g_sse_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_FUSED");
+    g_sse_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+hipError_t launch_sse_gcm(const SseGcmLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const gcm::Plan p = gcm::plan_for(a.n);
+  const uintptr_t src = reinterpret_cast<uintptr_t>(a.src), dst = reinterpret_cast<uintptr_t>(a.dst);
+  if (!t || !a.src || !a.dst || !a.part || a.n == 0 || p.nblocks > 0xFFFFFFFEull || src % 4 || (dst - src) % 16 ||
+      reinterpret_cast<uintptr_t>(a.part) % 16 || a.ntiles != p.ntiles || a.vfront != p.vfront || grid != p.grid)
+    return hipErrorInvalidValue;
+  if (src != dst && src < dst + a.n && dst < src + a.n) return hipErrorInvalidValue;  // in place or disjoint
+  const dim3 g(static_cast<unsigned>(grid)), b(kCrcWgThreads);
+  switch ((src & 15) >> 2) {
+    case 0: hipLaunchKernelGGL(sse_gcm_kernel<0>, g, b, 0, s, a, t); break;
+    case 1: hipLaunchKernelGGL(sse_gcm_kernel<1>, g, b, 0, s, a, t); break;
+    case 2: hipLaunchKernelGGL(sse_gcm_kernel<2>, g, b, 0, s, a, t); break;
+    default: hipLaunchKernelGGL(sse_gcm_kernel<3>, g, b, 0, s, a, t); break;
   }
   return hipGetLastError();
 }

@@ -36,6 +36,16 @@
 
 namespace dfs {
 
+// DFS_SSE_OFFLOAD=1: SSE PUT/GET bodies try the co-located chunkserver's GPU (fast-path op 10) before
+// OpenSSL on this thread. Off by default: see profiles/r10.
+static bool sse_offload() {
+  static const bool on = [] {
+    const char* e = std::getenv("DFS_SSE_OFFLOAD");
+    return e && std::atoi(e) != 0;
+  }();
+  return on;
+}
+
 namespace {
 
 constexpr size_t kMaxHead = 64 << 10;
@@ -1609,7 +1619,12 @@ bool S3Front::native_put(Conn* c, Req& r, const std::string& path, bool part) {
     dk = crypto::random_bytes(32);
     const std::string n1 = crypto::random_bytes(12), n2 = crypto::random_bytes(12);
     std::memcpy(dst, n1.data(), 12);
-    crypto::aes256gcm_encrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), dst, dst + 12, n, dst + 12 + n);
+    // the body's AES-GCM on the co-located chunkserver's GPU when it takes it, else here: same bytes
+    if (n && sse_offload() &&
+        fc_->sse_crypt(slot, 12, n, reinterpret_cast<const uint8_t*>(dk.data()), dst, true, dst + 12 + n, r.rid) == FastClient::Ok)
+      st_.sse_offloaded++;
+    else
+      crypto::aes256gcm_encrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), dst, dst + 12, n, dst + 12 + n);
     const std::string wrapped = n2 + crypto::aes256gcm_encrypt(cfg_.sse_kek, n2, dk, "");
     attrs["x-amz-sse-encrypted-dek"] = crypto::base64_encode(wrapped);
   }
@@ -2198,7 +2213,15 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
   if (got != size) return proxy(c, r, nullptr, 0, "short-read");
   uint8_t* b = fc_->slot_mut(slot);
   const uint64_t plen = size - 28;
-  if (!crypto::aes256gcm_decrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), b, b + 12, plen, b + 12 + plen))
+  // on the chunkserver's GPU when it takes it; an authentication failure there is as final as here
+  const FastClient::Status off =
+      plen && sse_offload()
+          ? fc_->sse_crypt(slot, 12, plen, reinterpret_cast<const uint8_t*>(dk.data()), b, false, b + 12 + plen, r.rid)
+          : FastClient::NotHandled;
+  if (off == FastClient::Failed) return proxy(c, r, nullptr, 0, "sse");
+  if (off == FastClient::Ok)
+    st_.sse_offloaded++;
+  else if (!crypto::aes256gcm_decrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), b, b + 12, plen, b + 12 + plen))
     return proxy(c, r, nullptr, 0, "sse");
   uint64_t s = 0, e = 0;
   int rng = parse_range(r.get("range"), plen, &s, &e);

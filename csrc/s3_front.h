@@ -96,7 +96,7 @@ struct S3FrontStats {
   // native GET/Range GET phases, summed microseconds: metadata stat, block read into the
   // slot, response send (where a GET's latency goes)
   uint64_t get_stat_us = 0, get_read_us = 0, get_send_us = 0, get_timed = 0;
-  uint64_t tls_handshakes = 0, tls_failures = 0, sse_puts = 0, sse_gets = 0, iam_native = 0, lists = 0, mpu_completes = 0, mpu_initiates = 0;
+  uint64_t tls_handshakes = 0, tls_failures = 0, sse_puts = 0, sse_gets = 0, sse_offloaded = 0, iam_native = 0, lists = 0, mpu_completes = 0, mpu_initiates = 0;
   uint64_t deletes = 0, multi_deletes = 0, deleted_keys = 0, mpu_aborts = 0, copies = 0, copy_bytes = 0;
   uint64_t chunked_puts = 0, chunk_sigs = 0, chunk_sig_failures = 0, presigned = 0, bucket_ops = 0;
   uint64_t sidecar_reads = 0, sidecar_writes = 0;  // the reference's <key>.meta files

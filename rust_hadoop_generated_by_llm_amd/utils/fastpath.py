@@ -12,7 +12,7 @@ import struct
 import threading
 import uuid
 
-OK, NOT_FOUND, OUT_OF_RANGE, CORRUPT, IO_ERROR, FENCED, UNSUPPORTED, BAD_REQUEST, PARTIAL_CORRUPT = range(9)
+OK, NOT_FOUND, OUT_OF_RANGE, CORRUPT, IO_ERROR, FENCED, UNSUPPORTED, BAD_REQUEST, PARTIAL_CORRUPT, AUTH_FAILED = range(10)
 
 _HDR = struct.Struct("<IB")
 _RESP = struct.Struct("<BQQH")
@@ -109,6 +109,16 @@ class FastPathClient:
         st, _total, _n, msg = self._call(6, body)
         self.last_ec_message = msg
         return st
+
+    def sse_crypt(self, shm_path: str, shm_off: int, length: int, key: bytes, nonce: bytes, encrypt: bool,
+                  tag: bytes = b"", request_id: str | None = None):
+        """AES-256-GCM of SSE-S3 in place over ``length`` bytes at ``shm_off`` of the client's arena on
+        the chunkserver's GPU (csrc/fastpath.cpp op 10). Returns (status, tag): OK, AUTH_FAILED, or
+        UNSUPPORTED when the kernel would not take it (the caller then uses its own CPU)."""
+        body = struct.pack("<BQQ", 1 if encrypt else 0, shm_off, length) + _s(key) + _s(nonce) + _s(tag)
+        body += _s(shm_path.encode()) + _s(self._rid(request_id))
+        st, _total, _n, msg = self._call(10, body)
+        return st, bytes.fromhex(msg) if st == OK else b""
 
     @staticmethod
     def _rid(request_id: str | None) -> bytes:

@@ -848,8 +848,109 @@ static int sse_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// --sse-read: ChunkStore::sse_read of a stored blob [nonce 12][ciphertext n][tag 16] into a registered
+// buffer: the one-kernel route against what a caller without it does (read_into of the whole blob,
+// then sse_crypt where the ciphertext lies, under sse_crypt's own floor, the plaintext left at + 12
+// and nothing moved), alternating in every repetition. One JSON line per
+// size; times are microseconds per call, each the mean of `iters` back-to-back calls, with the median
+// and the spread (max - min over the repetitions) of either route. `n` counts plaintext bytes.
+static int sse_read_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--sse-read needs a GPU\n");
+    return 1;
+  }
+  std::filesystem::remove_all(dir);
+  StoreConfig cfg;
+  cfg.storage_dir = dir + "/sse_read";
+  cfg.device = device;
+  cfg.hbm_capacity = 512ull << 20;
+  ChunkStore s(cfg);
+  uint8_t key[32], nonce[12];
+  for (int i = 0; i < 32; ++i) key[i] = static_cast<uint8_t>(3 * i + 1);
+  for (int i = 0; i < 12; ++i) nonce[i] = static_cast<uint8_t>(7 * i + 5);
+  int rc = 0;
+  for (uint64_t n : {64ull << 10, 1ull << 20, 4ull << 20, 16ull << 20, 100ull << 20}) {
+    const auto plain = random_bytes(n, static_cast<uint32_t>(n + 31));
+    std::vector<uint8_t> blob(n + 28);
+    std::memcpy(blob.data(), nonce, 12);
+    std::memcpy(blob.data() + 12, plain.data(), n);
+    crypto::aes256gcm_encrypt_inplace(key, nonce, blob.data() + 12, n, blob.data() + 12 + n);
+    const std::string id = "sse-" + std::to_string(n);
+    if (!s.write(id, blob.data(), blob.size(), 0).ok) return 1;
+    uint8_t* out = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void**>(&out), n + 64, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) return 1;
+    s.register_host(out, n + 64);
+    const int iters = static_cast<int>(std::clamp<uint64_t>((64ull << 20) / n, 2, 100));
+    std::vector<double> us[2];  // [0] staged, [1] fused
+    bool match = true;
+    auto run = [&](int fused, int count) {
+      set_sse_read_fused(fused != 0, 0);  // every size takes the kernel: the floor is what this measures
+      double t = 0;
+      for (int i = 0; i < count && match; ++i) {
+        std::memset(out, 0, 64);
+        std::string err;
+        if (fused) {
+          uint64_t got = 0;
+          const auto t0 = Clock::now();
+          const auto st = s.sse_read(id, key, out, n, &got, &err);
+          t += secs(t0, Clock::now());
+          match = st == ChunkStore::SseRead::Ok && got == n && std::memcmp(out, plain.data(), n) == 0;
+        } else {  // as a caller without sse_read does it: the blob into its slot, decrypted where it lies, sent from + 12
+          const auto t0 = Clock::now();
+          const ReadResult r = s.read_into(id, 0, n + 28, out);
+          const bool ok = r.status == ReadStatus::Ok && s.sse_crypt(out + 12, n, key, out, false, out + 12 + n, &err);
+          t += secs(t0, Clock::now());
+          match = ok && std::memcmp(out + 12, plain.data(), n) == 0;
+        }
+      }
+      return t * 1e6 / count;
+    };
+    for (int fused = 0; fused < 2; ++fused) run(fused, 2);  // warm-up: code objects, scratch, residency
+    const uint64_t before = s.stats().sse_fused_reads;
+    for (int rep = 0; rep < reps; ++rep)
+      for (int fused = 1; fused >= 0; --fused) us[fused].push_back(run(fused, iters));
+    match = match && s.stats().sse_fused_reads - before == static_cast<uint64_t>(reps) * iters;
+    auto list = [](const std::vector<double>& v) {
+      std::string o;
+      for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+      return o;
+    };
+    auto median = [](std::vector<double> v) {
+      std::sort(v.begin(), v.end());
+      return v[v.size() / 2];
+    };
+    auto spread = [](const std::vector<double>& v) { return *std::max_element(v.begin(), v.end()) - *std::min_element(v.begin(), v.end()); };
+    std::printf("{\"sse_read\": {\"bytes\": %llu, \"iters\": %d, \"fused_us\": [%s], \"staged_us\": [%s], "
+                "\"fused_median_us\": %.1f, \"staged_median_us\": %.1f, \"fused_spread_us\": %.1f, "
+                "\"staged_spread_us\": %.1f, \"fused_gbps\": %.2f, \"staged_gbps\": %.2f, \"match\": %s}}\n",
+                static_cast<unsigned long long>(n), iters, list(us[1]).c_str(), list(us[0]).c_str(), median(us[1]),
+                median(us[0]), spread(us[1]), spread(us[0]), n / median(us[1]) / 1e3, n / median(us[0]) / 1e3,
+                match ? "true" : "false");
+    std::fflush(stdout);
+    if (!match) rc = 1;
+    s.unregister_host(out);
+    (void)hipHostFree(out);
+    s.remove(id);
+  }
+  set_sse_read_fused(true, static_cast<int64_t>(kSseReadFusedMinBytes));
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 int main(int argc, char** argv) {
   dfs::trace_init();  // before any thread: roctx's first range calls setenv (trace.h)
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--sse-read") {
+      std::string dir = "/tmp/io_bench_sse_read";
+      int device = 0, reps = 5;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return sse_read_bench(device, dir, std::max(5, reps));
+    }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--sse") {
       std::string dir = "/tmp/io_bench_sse";

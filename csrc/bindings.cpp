@@ -249,6 +249,13 @@ PYBIND11_MODULE(_dfs_native, m) {
   m.def("set_sse_fused", &set_sse_fused, "SSE AES-256-GCM of registered bodies in one kernel (else OpenSSL)",
         py::arg("on"), py::arg("min_bytes") = -1);
   m.def("sse_fused_min_bytes", &sse_fused_min_bytes, "bodies below this many bytes stay on OpenSSL");
+  m.def("set_sse_read_fused", &set_sse_read_fused,
+        "GETs of stored SSE-S3 blobs verified, decrypted and delivered by one kernel (else read, then sse_crypt)",
+        py::arg("on"), py::arg("min_bytes") = -1);
+  m.def("sse_read_fused_min_bytes", &sse_read_fused_min_bytes, "blobs with less plaintext than this stay staged");
+  // the shape of an sse_read_kernel launch: bytes of the blob per workgroup step, and the grid's cap
+  m.attr("sse_read_tile_bytes") = kSseReadTileBytes;
+  m.attr("sse_read_max_grid") = static_cast<int>(gcm::kGcmMaxGrid);
   m.def("set_ec_read_fused", &set_ec_read_fused, "degraded EC range reads in one kernel (else decode into HBM, then copies)");
   m.def("set_crc_wide", &set_crc_wide, "K1/K2 one workgroup per CU: 0 off, 1 shared LDS image, 2 + LDS basis");
   m.def("set_crc_kernels", [](bool mfma, int scrub_ring, int tile_ring) {
@@ -544,6 +551,27 @@ PYBIND11_MODULE(_dfs_native, m) {
         if (!ok) throw std::runtime_error(err);
         return py::bytes(t);
       }, py::arg("buffer"), py::arg("key"), py::arg("nonce"), py::arg("encrypt"), py::arg("tag") = py::bytes())
+      // GET of a stored SSE-S3 blob [nonce][ciphertext][tag]: the plaintext into a writable buffer
+      // of at least that many bytes, nothing behind it written. Returns (status, n): 0 Ok, 1 NotFound, 2 Corrupt (n = the
+      // bad slice), 3 AuthFailed, 4 IoError.
+      .def("sse_read", [](ChunkStore& s, const std::string& id, py::bytes key, py::buffer out) {
+        py::buffer_info bi = out.request(true);
+        std::string k = key, err;
+        if (k.size() != 32) throw std::invalid_argument("sse_read: 32-byte key");
+        uint64_t n = 0;
+        int64_t bad = -1;
+        ChunkStore::SseRead st;
+        {
+          py::gil_scoped_release rel;
+          st = s.sse_read(id, reinterpret_cast<const uint8_t*>(k.data()), static_cast<uint8_t*>(bi.ptr),
+                          static_cast<uint64_t>(bi.size * bi.itemsize), &n, &err, &bad);
+        }
+        gcm::wipe(&k[0], k.size());
+        return py::make_tuple(static_cast<int>(st), st == ChunkStore::SseRead::Corrupt ? static_cast<uint64_t>(bad) : n);
+      }, py::arg("block_id"), py::arg("key"), py::arg("out_buffer"))
+      .def("sse_read_fusable", [](ChunkStore& s, const std::string& id, py::buffer out) {
+        return s.sse_read_fusable(id, static_cast<const uint8_t*>(out.request().ptr));
+      })
       // degraded read: bytes [offset, offset + length) of the RS(k, m) file whose k + m shards are
       // the resident blocks `block_ids` ("" = lost) into `out`; a registered `out` takes the
       // single-kernel path. Returns the number of bytes placed, None on failure.
@@ -900,6 +928,29 @@ PYBIND11_MODULE(_dfs_native, m) {
       throw std::runtime_error("gcm_ghash: AES block encryption failed");
     return py::bytes(reinterpret_cast<const char*>(out), 16);
   }, py::arg("key"), py::arg("data"), py::arg("grid") = 0);
+  // The host half of sse_read_kernel: whether `tag` authenticates `ciphertext` under (key, nonce),
+  // with H and its powers prepared before the nonce is known, the message front-aligned on whole
+  // tiles, the partials as the kernel leaves them and the zero blocks behind the message taken
+  // into account by gcm::tag_matches.
+  m.def("gcm_tag_matches", [](py::bytes key, py::bytes nonce, py::bytes ciphertext, py::bytes tag, int grid) {
+    std::string k = key, nc = nonce, c = ciphertext, t = tag;
+    if (k.size() != 32 || nc.size() != 12 || t.size() != 16 || c.empty())
+      throw std::invalid_argument("gcm_tag_matches: 32-byte key, 12-byte nonce, 16-byte tag, a ciphertext");
+    const uint64_t n = c.size();
+    const uint8_t* kp = reinterpret_cast<const uint8_t*>(k.data());
+    const gcm::Plan p = gcm::plan_for((n + 28 + (16 << 10) - 1) / (16 << 10) * (16 << 10), grid);
+    c.resize(p.nblocks * 16, '\0');
+    gcm::Keys keys;
+    std::vector<gcm::U128> part(static_cast<size_t>(p.grid));
+    bool ok = gcm::prepare_keyed(kp, p, &keys);
+    if (ok) gcm::ghash_partials(keys, p, reinterpret_cast<const uint8_t*>(c.data()), c.size(), part.data());
+    ok = ok && gcm::set_nonce(kp, reinterpret_cast<const uint8_t*>(nc.data()), &keys) &&
+         gcm::tag_matches(keys, gcm::ghash_fold(keys, p, part.data()), n, p.nblocks - (n + 15) / 16,
+                          reinterpret_cast<const uint8_t*>(t.data()));
+    gcm::wipe(&keys, sizeof(keys));
+    gcm::wipe(&k[0], k.size());
+    return ok;
+  }, py::arg("key"), py::arg("nonce"), py::arg("ciphertext"), py::arg("tag"), py::arg("grid") = 0);
   m.def("rsa_sha256_verify", [](py::bytes n, py::bytes e, py::bytes msg, py::bytes sig) {
     return crypto::rsa_sha256_verify(n, e, msg, sig);
   });

@@ -2563,6 +2563,7 @@ StoreStats ChunkStore::stats() {
   s.ec_fused_decodes = ec_fused_decodes_.load();
   s.ec_fused_reads = ec_fused_reads_.load();
   s.sse_fused_crypts = sse_fused_crypts_.load();
+  s.sse_fused_reads = sse_fused_reads_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -4153,6 +4154,157 @@ bool ChunkStore::sse_crypt(uint8_t* p, uint64_t n, const uint8_t key[32], const 
   if (crypto::aes256gcm_decrypt_inplace(key, nonce, p, n, tag)) return true;
   *err = kSseAuthFailed;
   return false;
+}
+
+namespace {
+// The lane's pinned scratch of an sse_read_kernel launch: GHASH partials, verdicts, nonce and tag.
+constexpr uint64_t kSseReadBadOff = gcm::kGcmMaxGrid * sizeof(gcm::U128);
+constexpr uint64_t kSseReadNonceTagOff = kSseReadBadOff + gcm::kGcmMaxGrid * sizeof(uint32_t);
+constexpr uint64_t kSseReadScratch = kSseReadNonceTagOff + 32;
+}  // namespace
+
+// The block pinned in HBM when sse_read_kernel would take it into `out` (the caller unpins), else null.
+const uint8_t* ChunkStore::sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size) {
+  if (!gpu() || !sse_read_fused_enabled() || !crc_mfma_enabled() || reinterpret_cast<uintptr_t>(out) % 16) return nullptr;
+  HIP_OK(hipSetDevice(cfg_.device));
+  const uint8_t* d = pin_device(id, size);
+  if (!d) return nullptr;
+  if (*size >= 29 && *size - 28 >= sse_read_fused_min_bytes() && sse_read_tiles(*size - 28) <= (0xFFFFFFFEull >> 10) &&
+      device_view(out, *size - 28) != nullptr)
+    return d;
+  unpin(id);
+  return nullptr;
+}
+
+bool ChunkStore::sse_read_fusable(const std::string& id, const uint8_t* out) {
+  uint64_t size = 0;
+  if (!sse_read_pin(id, out, &size)) return false;
+  unpin(id);
+  return true;
+}
+
+ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t key[32], uint8_t* out, uint64_t out_cap,
+                                         uint64_t* n_out, std::string* err, int64_t* bad_slice, bool fused_only) {
+  TraceRange tr("dfs.store.sse_read");  // no key material in ranges, logs or errors
+  *n_out = 0;
+  if (bad_slice) *bad_slice = -1;
+  uint64_t size = 0;
+  const uint8_t* d = sse_read_pin(id, out, &size);
+  if (!d) {
+    const int64_t have = block_size(id);
+    if (have < 0) {
+      *err = "Block not found";
+      return SseRead::NotFound;
+    }
+    size = static_cast<uint64_t>(have);
+  }
+  if (size < 29 || size - 28 > out_cap) {
+    if (d) unpin(id);
+    *err = size < 29 ? "not an SSE blob: " + std::to_string(size) + " bytes"
+                     : "buffer of " + std::to_string(out_cap) + " bytes for " + std::to_string(size - 28) + " of plaintext";
+    return SseRead::IoError;
+  }
+  if (d) {
+    uint8_t* dout = device_view(out, size - 28);
+    const uint64_t n = size - 28, ntiles = sse_read_tiles(n);
+    const gcm::Plan plan = gcm::plan_for(kSseReadTileBytes * ntiles);
+    Lane* l = acquire_lane();
+    ensure_hscratch(l, kSseReadScratch);
+    // Nothing below throws: the lane and the pin are released and every copy of the key schedule
+    // and the powers of H that the store owns is wiped on each way out. A launch that fails has
+    // written nothing, so the call goes on to the staged route; a failed synchronise is an error.
+    gcm::Keys keys;
+    SseReadLaunch a{};
+    hipError_t launched = hipErrorNotReady, synced = hipSuccess;
+    uint32_t bad = 0xFFFFFFFFu;
+    bool authentic = false;
+    if (l->hscratch_dev && gcm::prepare_keyed(key, plan, &keys)) {
+      uint8_t* hdev = static_cast<uint8_t*>(l->hscratch_dev);
+      a.src = d;
+      a.meta = reinterpret_cast<const uint32_t*>(d + align_up(size, 256));
+      a.out = dout;
+      a.n = n;
+      a.ntiles = ntiles;
+      a.full_init = crc_init_term(kSliceBytes);
+      a.tail_init = size % kSliceBytes ? crc_init_term(size % kSliceBytes) : 0;
+      std::memcpy(a.rk, keys.rk, sizeof(a.rk));
+      a.h = keys.h;
+      a.hjump = keys.hjump;
+      std::memcpy(a.tree, keys.tree, sizeof(a.tree));
+      a.part = reinterpret_cast<gcm::U128*>(hdev);
+      a.part_bad = reinterpret_cast<uint32_t*>(hdev + kSseReadBadOff);
+      a.nonce_tag = hdev + kSseReadNonceTagOff;
+      launched = launch_sse_read(a, dtables_, plan.grid, l->stream);
+      if (launched == hipSuccess) {
+        launches_++;
+        synced = hipStreamSynchronize(l->stream);
+        if (synced == hipSuccess) {
+          for (int g = 0; g < plan.grid; ++g)
+            bad = std::min(bad, reinterpret_cast<const uint32_t*>(l->hscratch + kSseReadBadOff)[g]);
+          // the kernel read the nonce where it lies; E_K(J0) and the comparison are the host's
+          const uint8_t* nt = l->hscratch + kSseReadNonceTagOff;
+          authentic = bad == 0xFFFFFFFFu && gcm::set_nonce(key, nt, &keys) &&
+                      gcm::tag_matches(keys, gcm::ghash_fold(keys, plan, reinterpret_cast<const gcm::U128*>(l->hscratch)),
+                                       n, plan.nblocks - (n + 15) / 16, nt + 12);
+        }
+        gcm::wipe(l->hscratch, plan.grid * sizeof(gcm::U128));
+      }
+    }
+    gcm::wipe(&a, sizeof(a));
+    gcm::wipe(&keys, sizeof(keys));
+    release_lane(l);
+    unpin(id);
+    if (launched == hipSuccess) {
+      if (synced != hipSuccess) {
+        *err = std::string("SSE read kernel: ") + hipGetErrorString(synced);
+        return SseRead::IoError;
+      }
+      sse_fused_reads_++;
+      if (authentic) {
+        *n_out = n;
+        return SseRead::Ok;
+      }
+      std::memset(out, 0, n);  // plaintext of a blob that did not verify is nobody's
+      if (bad != 0xFFFFFFFFu) {
+        std::lock_guard<std::mutex> g(mu_);
+        ++st_.crc_mismatches;
+        if (bad_slice) *bad_slice = bad;
+        *err = "Checksum mismatch at chunk " + std::to_string(bad);
+        return SseRead::Corrupt;
+      }
+      *err = kSseAuthFailed;
+      return SseRead::AuthFailed;
+    }
+    (void)hipGetLastError();
+  }
+  if (fused_only) {
+    *err = "the kernel does not take this read";
+    return SseRead::Declined;
+  }
+  // staged: the ciphertext straight to out[0, n), nonce and tag beside it on the stack, then
+  // sse_crypt where the ciphertext lies. The three ranges touch every slice of the blob between
+  // them, so a bad slice anywhere is found; no byte of `out` behind n is written.
+  const uint64_t n = size - 28;
+  uint8_t nonce_tag[28];
+  const struct {
+    uint64_t off, len;
+    uint8_t* to;
+  } parts[3] = {{12, n, out}, {0, 12, nonce_tag}, {12 + n, 16, nonce_tag + 12}};
+  for (const auto& p : parts) {
+    const ReadResult r = read_into(id, p.off, p.len, p.to);
+    if (r.status == ReadStatus::Ok && !r.partial_corrupt) continue;
+    std::memset(out, 0, n);
+    *err = r.error;
+    if (bad_slice) *bad_slice = r.bad_slice;
+    return r.status == ReadStatus::NotFound ? SseRead::NotFound
+           : r.status == ReadStatus::Corrupt || r.partial_corrupt ? SseRead::Corrupt : SseRead::IoError;
+  }
+  if (!sse_crypt(out, n, key, nonce_tag, false, nonce_tag + 12, err)) {
+    std::memset(out, 0, n);
+    return *err == kSseAuthFailed ? SseRead::AuthFailed : SseRead::IoError;
+  }
+  *n_out = n;
+  return SseRead::Ok;
 }
 
 bool ChunkStore::device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n) {

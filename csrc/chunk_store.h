@@ -96,6 +96,7 @@ struct StoreStats {
   uint64_t ec_fused_decodes = 0;  // shard sets rebuilt and checksummed by one ec_fused_kernel launch
   uint64_t ec_fused_reads = 0;    // degraded EC range reads served by one ec_read_kernel launch
   uint64_t sse_fused_crypts = 0;  // SSE bodies encrypted or decrypted by one sse_gcm_kernel launch
+  uint64_t sse_fused_reads = 0;   // stored SSE blobs verified, decrypted and delivered by one sse_read_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -324,6 +325,20 @@ class ChunkStore {
   bool sse_fusable(const uint8_t* p, uint64_t n);  // would sse_crypt take the kernel for p[0, n)
   bool sse_crypt(uint8_t* p, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt, uint8_t tag[16],
                  std::string* err);
+  // A GET of an SSE-S3 object: block `id` holds [nonce 12][ciphertext n][tag 16]; its n plaintext
+  // bytes end up at out[0, n), *n is set, out_cap >= n, and nothing behind out + n is written. On a
+  // GPU store, with the block resident in HBM, `out` registered and 16 B aligned and n at or above
+  // sse_read_fused_min_bytes(): one sse_read_kernel launch verifies every slice, authenticates,
+  // decrypts and stores the plaintext. Otherwise the staged route: read_into of the ciphertext
+  // straight to `out` and of nonce and tag to the stack, then sse_crypt on `out`; no bulk move.
+  // Statuses and bytes are the same either way: Corrupt sets *bad_slice and counts in
+  // crc_mismatches, AuthFailed has *err = kSseAuthFailed, and both leave out[0, n) zeroed. With
+  // fused_only the call answers Declined instead of taking the staged route (the fast path, whose
+  // caller then reads its own way). The key schedule and the powers of H are wiped before this returns.
+  enum class SseRead : int { Ok = 0, NotFound = 1, Corrupt = 2, AuthFailed = 3, IoError = 4, Declined = 5 };
+  bool sse_read_fusable(const std::string& id, const uint8_t* out);  // would sse_read take the kernel
+  SseRead sse_read(const std::string& id, const uint8_t key[32], uint8_t* out, uint64_t out_cap, uint64_t* n,
+                   std::string* err, int64_t* bad_slice = nullptr, bool fused_only = false);
   // Device bytes into host memory (registered: one DMA) and synchronously complete.
   bool device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n);
   // A copy of device bytes committed as block `id` (checksummed, verified, made durable).
@@ -526,8 +541,9 @@ class ChunkStore {
   // block of n bytes.
   bool ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
                 std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
+  const uint8_t* sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size);
   std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0},
-      sse_fused_crypts_{0};
+      sse_fused_crypts_{0}, sse_fused_reads_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

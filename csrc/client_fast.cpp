@@ -804,6 +804,43 @@ FastClient::Status FastClient::sse_crypt(uint64_t off, uint64_t n, const uint8_t
   return Ok;
 }
 
+FastClient::Status FastClient::sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
+                                        const std::string& rid_in) {
+  const std::string rid = rid_in.empty() ? new_request_id() : rid_in;
+  RequestScope rs(rid);
+  if (!base_) return NotHandled;
+  pb::FileMetadata m;
+  if (!m.decode(meta_pb) || m.blocks.size() != 1 || m.blocks[0].ec_data_shards > 0 || m.size < 29 || m.size > slot_bytes_)
+    return NotHandled;
+  const pb::BlockInfo& b = m.blocks[0];
+  bool local = false;
+  for (auto& l : b.locations) local |= strip_scheme(l) == local_cs_;
+  if (!local) return NotHandled;
+  const int64_t s = acquire(slot_bytes_);
+  if (s < 0) return NotHandled;
+  std::string body;
+  put<uint64_t>(body, static_cast<uint64_t>(s));
+  put<uint64_t>(body, slot_bytes_);
+  put_str(body, b.block_id);
+  put_str(body, std::string(reinterpret_cast<const char*>(key), 32));
+  put_str(body, arena_path_);
+  put_str(body, rid);
+  uint8_t st = 0;
+  uint64_t total = 0, got = 0;
+  std::string fmsg;
+  const bool sent = fp_call(11, body, &st, &total, &got, &fmsg);
+  gcm::wipe(&body[0], body.size());
+  if (!sent || st != 0 || got + 28 != m.size) {
+    release(s);
+    return sent && st == 9 ? Failed : NotHandled;  // FpStatus::AuthFailed is final; anything else is the caller's own read
+  }
+  *slot = s;
+  *n = got;
+  reads_++;
+  sse_gpu_++;
+  return Ok;
+}
+
 FastClient::Status FastClient::write_ec(const std::string& path, const uint8_t* data, size_t n, int k, int m,
                                         std::string* msg, const std::string& rid_in) {
   const std::string rid = rid_in.empty() ? new_request_id() : rid_in;

@@ -973,6 +973,43 @@ void FastPathServer::serve(int fd) {
       }
       gcm::wipe(&key[0], key.size());
       gcm::wipe(body.data(), body.size());
+    } else if (op == 11) {  // SSE_READ: a stored SSE-S3 blob verified, decrypted and delivered by one kernel
+      const uint64_t off = rd.get<uint64_t>(), cap = rd.get<uint64_t>();
+      std::string id = rd.str(), key = rd.str(), path = rd.str();
+      std::string rid = rd.p < rd.end ? rd.str() : std::string();
+      RequestScope rs(rid);
+      note_rid(rid);
+      TraceRange tr("dfs.fp.sse_read");  // the key stays out of ranges, logs and answers
+      std::string err;
+      uint8_t* base = nullptr;
+      if (!rd.ok || id.empty() || key.size() != 32 || cap == 0 || cap > kMaxTransfer || off > (1ull << 62)) {
+        sent = send_response(fd, FpStatus::BadRequest, 0, 0, "malformed sse read request");
+      } else if ((base = map_shm(path, off, cap, &err)) == nullptr) {
+        sent = send_response(fd, FpStatus::Unsupported, 0, 0, "short-circuit unavailable: " + err);
+      } else {
+        if (store_->gpu()) {  // a new arena is pinned off this thread: the first read waits for that instead of losing the GPU
+          std::unique_lock<std::mutex> lk(mu_);
+          workers_cv_.wait(lk, [this] { return pending_regs_ == 0; });
+        }
+        uint64_t n = 0;
+        int64_t bad = -1;
+        // the kernel or nothing: one residency check and one pin, inside the call
+        switch (store_->sse_read(id, reinterpret_cast<const uint8_t*>(key.data()), base + off, cap, &n, &err, &bad, true)) {
+          case ChunkStore::SseRead::Ok:
+            bump(&FpStats::sse_reads);
+            sent = send_response(fd, FpStatus::Ok, n + 28, n, "");
+            break;
+          case ChunkStore::SseRead::NotFound: sent = send_response(fd, FpStatus::NotFound, 0, 0, err); break;
+          case ChunkStore::SseRead::Corrupt: sent = send_response(fd, FpStatus::Corrupt, 0, 0, err); break;
+          case ChunkStore::SseRead::AuthFailed: sent = send_response(fd, FpStatus::AuthFailed, 0, 0, err); break;
+          case ChunkStore::SseRead::Declined:
+            sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU, slot not pinned, block not resident or below the kernel's floor");
+            break;
+          default: sent = send_response(fd, FpStatus::IoError, 0, 0, err); break;
+        }
+      }
+      gcm::wipe(&key[0], key.size());
+      gcm::wipe(body.data(), body.size());
     } else if (op == 7) {  // EC_WRITE: encode in HBM, scatter the shards over the engine
       sent = ec_write(fd, body.data() + 1, body.data() + n);
     } else if (op == 8) {  // EC_READ: gather the surviving shards into HBM, decode there

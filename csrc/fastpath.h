@@ -41,6 +41,12 @@
 //               the client's slot, by sse_gcm_kernel; answers Ok with the tag as 32 hex digits in msg,
 //               AuthFailed, or Unsupported when the kernel would not take it (no GPU, slot not pinned,
 //               below the store's floor): the client then encrypts on its own CPU
+//     op 11 SSE_READ: u64 shm_off | u64 cap | u16 id | u16 key(32) | u16 path [| u16 rid]  -- GET of the stored
+//               SSE-S3 blob `id` ([nonce][ciphertext][tag]) by sse_read_kernel: verified, authenticated,
+//               decrypted, and only the plaintext stored at the front of the client's slot; answers Ok with
+//               total = the blob's size and bytes = n, NotFound, Corrupt, AuthFailed, or Unsupported when
+//               ChunkStore::sse_read_fusable says the kernel would not take it: the client then reads and
+//               decrypts its own way. The key crosses only this peer-checked abstract socket.
 //   response = u32 body_len | u8 status | u64 total | u64 bytes | u16 msg_len msg
 //   (for WRITE/REPL ``bytes`` carries replicas_written; for CTRL ``msg`` is the engine reply)
 //
@@ -89,6 +95,7 @@ struct FpStats {
   uint64_t p2p_fallbacks = 0;     // replicas moved to shared memory after a P2P failure
   uint64_t ec_ops = 0;            // erasure-coding matrix products run for clients
   uint64_t sse_crypts = 0;        // SSE bodies encrypted or decrypted in clients' slots
+  uint64_t sse_reads = 0;         // stored SSE blobs decrypted into clients' slots by one kernel
   uint64_t heals_out = 0, heals_in = 0;  // heal / balancer copies sent / received on the engine
   uint64_t sliced_writes = 0;  // head writes whose replica sends overlapped the staging
   // device-resident erasure coding: EC writes whose shards were encoded and scattered HBM ->

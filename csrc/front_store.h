@@ -74,6 +74,13 @@ class FrontStore {
     (void)slot, (void)off, (void)n, (void)key, (void)nonce, (void)encrypt, (void)tag, (void)rid;
     return FastClient::NotHandled;
   }
+  // GET of a stored SSE-S3 blob decrypted where it is stored (FastClient::sse_read): Ok leaves the
+  // plaintext at the front of *slot. NotHandled, the default: the caller reads and decrypts itself.
+  virtual Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
+                          const std::string& rid) {
+    (void)meta_pb, (void)key, (void)slot, (void)n, (void)rid;
+    return FastClient::NotHandled;
+  }
   // calls a first-choice path declined and a second one served (LocalFirstFrontStore)
   virtual uint64_t fallbacks() const { return 0; }
 };
@@ -116,6 +123,10 @@ class FastFrontStore final : public FrontStore {
   Status sse_crypt(int64_t slot, uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt,
                    uint8_t tag[16], const std::string& rid) override {
     return slot < 0 ? FastClient::NotHandled : fc_->sse_crypt(static_cast<uint64_t>(slot) + off, n, key, nonce, encrypt, tag, rid);
+  }
+  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
+                  const std::string& rid) override {
+    return fc_->sse_read(meta_pb, key, slot, n, rid);
   }
 
  private:
@@ -193,6 +204,10 @@ class LocalFirstFrontStore final : public FrontStore {
   Status sse_crypt(int64_t slot, uint64_t off, uint64_t n, const uint8_t key[32], const uint8_t nonce[12], bool encrypt,
                    uint8_t tag[16], const std::string& rid) override {
     return slot < 0 ? FastClient::NotHandled : fc_->sse_crypt(static_cast<uint64_t>(slot) + off, n, key, nonce, encrypt, tag, rid);
+  }
+  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
+                  const std::string& rid) override {
+    return fc_->sse_read(meta_pb, key, slot, n, rid);
   }
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid) override {
     if (fc_->list_components(prefix, out, rid) == FastClient::Ok) return FastClient::Ok;

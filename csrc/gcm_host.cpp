@@ -141,6 +141,32 @@ bool prepare(const uint8_t key[32], const uint8_t nonce[12], const Plan& p, Keys
   return true;
 }
 
+bool prepare_keyed(const uint8_t key[32], const Plan& p, Keys* k) {
+  const uint8_t none[12] = {0};
+  if (!prepare(key, none, p, k)) return false;
+  wipe(k->ekj0, sizeof(k->ekj0));  // of the zero nonce: nobody's
+  return true;
+}
+
+bool set_nonce(const uint8_t key[32], const uint8_t nonce[12], Keys* k) {
+  uint8_t blk[16] = {0};
+  std::memcpy(k->nonce, nonce, 12);
+  std::memcpy(blk, nonce, 12);
+  blk[15] = 1;
+  return aes256_ecb_block(key, blk, k->ekj0);
+}
+
+bool tag_matches(const Keys& k, U128 folded, uint64_t n, uint64_t vback, const uint8_t tag[16]) {
+  uint8_t g[16];
+  for (int i = 0; i < 16; ++i) g[i] = tag[i] ^ k.ekj0[i];
+  const U128 want = from_bytes(g), len = gf128_mul(k.h, U128{0, n * 8});
+  const U128 lhs = gf128_mul(k.h, folded);
+  const U128 rhs = gf128_mul(gf128_pow(k.h, vback), U128{want.hi ^ len.hi, want.lo ^ len.lo});
+  const bool ok = CRYPTO_memcmp(&lhs, &rhs, sizeof(lhs)) == 0;
+  wipe(g, sizeof(g));
+  return ok;
+}
+
 void ghash_partials(const Keys& k, const Plan& p, const uint8_t* data, uint64_t n, U128* part) {
   constexpr int kLanes = kGcmTileBlocks / kGcmLaneBlocks;
   std::vector<U128> acc(kLanes);

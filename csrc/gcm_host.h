@@ -132,6 +132,16 @@ void aes256_expand_key(const uint8_t key[32], uint32_t rk[60]);
 U128 gf128_pow(U128 h, uint64_t e);
 // Everything in Keys. Single block encryptions go through OpenSSL; false if it refuses.
 bool prepare(const uint8_t key[32], const uint8_t nonce[12], const Plan& p, Keys* k);
+// For a message whose nonce the host learns only after the kernel ran (sse_read_kernel reads it
+// from the stored blob): everything in Keys that needs the key alone; `nonce` and `ekj0` stay zero
+// until set_nonce fills them.
+bool prepare_keyed(const uint8_t key[32], const Plan& p, Keys* k);
+bool set_nonce(const uint8_t key[32], const uint8_t nonce[12], Keys* k);
+// Whether `tag` authenticates an n-byte message whose blocks were folded with `vback` zero blocks
+// behind them, so that `folded` is the message's sum times H^vback. Zero blocks at the end do
+// change GHASH and H has no cheap inverse, so the comparison is made one multiply further on, where
+// both sides can be computed: folded * H == ((tag ^ E_K(J0)) ^ len * H) * H^vback. Constant time.
+bool tag_matches(const Keys& k, U128 folded, uint64_t n, uint64_t vback, const uint8_t tag[16]);
 // The workgroup partials as the kernel leaves them, computed on the host: [p.grid].
 void ghash_partials(const Keys& k, const Plan& p, const uint8_t* data, uint64_t n, U128* part);
 // Fold per-workgroup partials into sum C_i * H^(nblocks - i), close with the length block

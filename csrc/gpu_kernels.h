@@ -17,6 +17,9 @@
 //   K7     sse_gcm_kernel: the AES-256-GCM of SSE-S3 over a body in registered host memory — CTR
 //          keystream from a T-table in LDS, XOR in place, and the GHASH of the ciphertext as
 //          per-workgroup partials that the host folds into the tag.
+//   K7 read  sse_read_kernel: a GET of an SSE-S3 object in one pass over its stored blob in HBM —
+//          the slices verified on the matrix cores, the ciphertext authenticated and decrypted in
+//          registers, and only the plaintext stored over PCIe into the reader's registered buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -280,6 +283,42 @@ bool sse_fused_enabled();
 uint64_t sse_fused_min_bytes();
 void set_sse_fused(bool on, int64_t min_bytes = -1);
 hipError_t launch_sse_gcm(const SseGcmLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// K7 read (sse_read_kernel): a stored SSE-S3 blob [nonce 12][ciphertext n][tag 16], resident in HBM
+// at `src` (16 B aligned, readable up to the next 16 B boundary behind its end) with its .meta
+// image `meta`, is verified slice by slice, decrypted and stored as n plaintext bytes at `out`, the
+// 16 B aligned device view of registered host memory: only [out, out + n) is written. The kernel
+// reads the nonce from the block; the host learns it, and the stored tag, from `nonce_tag`.
+// `part_bad` takes the per-workgroup minimum bad slice (0xFFFFFFFF: none) and `part` the GHASH
+// partials of the plan gcm::plan_for(kSseReadTileBytes * ntiles), ntiles = sse_read_tiles(n), whose
+// grid is the launch's; gcm::prepare_keyed for that plan gives the key schedule and the powers of
+// H, and gcm::tag_matches with the plan's zero blocks behind the message closes the tag. part,
+// part_bad and nonce_tag are device-visible host words.
+constexpr uint64_t kSseReadTileBytes = 16 << 10;
+inline uint64_t sse_read_tiles(uint64_t n) { return (n + 28 + kSseReadTileBytes - 1) / kSseReadTileBytes; }
+struct SseReadLaunch {
+  const uint8_t* src;
+  const uint32_t* meta;
+  uint8_t* out;
+  uint64_t n, ntiles;
+  uint32_t full_init, tail_init;  // S(512), S((n + 28) % 512)
+  uint32_t rk[60];
+  gcm::U128 h, hjump, tree[gcm::kGcmTreeSteps];
+  gcm::U128* part;     // [grid]
+  uint32_t* part_bad;  // [grid]
+  uint8_t* nonce_tag;  // [28]
+};
+// DFS_SSE_READ_FUSED=0 keeps the staged route (read_into, then sse_crypt where the blob lies), and
+// blobs whose plaintext is below sse_read_fused_min_bytes() stay on it. DFS_SSE_READ_FUSED_MIN_BYTES
+// overrides the floor; set_sse_read_fused is the benches' and tests' switch (min_bytes < 0 keeps it).
+// A call costs ~128 us before the first byte (K7's fixed cost: key schedule, launch, synchronise,
+// GHASH tree), which the staged route undercuts at 64 KiB with a mirror read and OpenSSL; 1 MiB is
+// the smallest measured size the kernel wins (profiles/r11).
+constexpr uint64_t kSseReadFusedMinBytes = 1ull << 20;
+bool sse_read_fused_enabled();
+uint64_t sse_read_fused_min_bytes();
+void set_sse_read_fused(bool on, int64_t min_bytes = -1);
+hipError_t launch_sse_read(const SseReadLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

@@ -1881,6 +1881,65 @@ __device__ __forceinline__ void sse_store(uint8_t* dst, int64_t pos, int64_t n, 
   }
 }
 
+// sse_gcm_kernel's AES and GHASH steps as functions, for sse_read_kernel.
+// Te0 and the S-box from the uploaded image into LDS (256 threads, one entry each; sync after).
+__device__ __forceinline__ void sse_load_tables(const DevCrcTables* __restrict__ gt, uint32_t (&te0)[256],
+                                                uint8_t (&sbox)[256]) {
+  const uint8_t* img = reinterpret_cast<const uint8_t*>(gt) + sizeof(DevCrcTables) + kSseTablesOffset;
+  te0[threadIdx.x] = reinterpret_cast<const uint32_t*>(img)[threadIdx.x];
+  sbox[threadIdx.x] = img[1024 + threadIdx.x];
+}
+
+// CTR keystream of message blocks j0 .. j0 + 3: E_K(nonce || 2 + j).
+template <class RK>
+__device__ __forceinline__ void sse_keystream(const uint32_t (&te0)[256], const uint8_t (&sbox)[256], const RK& rk,
+                                              uint32_t n0, uint32_t n1, uint32_t n2, int64_t j0, uint32_t (&ks)[4][4]) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    ks[b][0] = n0;
+    ks[b][1] = n1;
+    ks[b][2] = n2;
+    ks[b][3] = gcm::bswap32(2u + static_cast<uint32_t>(j0 + b));
+  }
+  gcm::aes256_encrypt_words<4>(te0, sbox, rk, ks);
+}
+
+// Mask of the bytes of a dword that has `left` message bytes at and behind its first one.
+__device__ __forceinline__ uint32_t sse_keep(int64_t left) {
+  return left >= 4 ? ~0u : left <= 0 ? 0u : (1u << (8 * left)) - 1u;
+}
+
+// One GHASH step: (acc ^ C) * H for the ciphertext block c (little-endian dwords).
+__device__ __forceinline__ gcm::U128 ghash_absorb(const gcm::U128& acc, const gcm::U128& h, const uint32_t (&c)[4]) {
+  const gcm::U128 e = gcm::ghash_element(c[0], c[1], c[2], c[3]);
+  return gcm::gf128_mul(h, gcm::U128{acc.hi ^ e.hi, acc.lo ^ e.lo});
+}
+
+// The lanes' accumulators, each standing at the end of its four blocks in the workgroup's last
+// tile, into the workgroup's partial: a log tree inside each wave, then the four waves in order.
+__device__ __forceinline__ void ghash_wg_partial(gcm::U128 acc, const gcm::U128 (&tree)[gcm::kGcmTreeSteps],
+                                                 gcm::U128 (&wave_part)[4], gcm::U128* part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll 1
+  for (int s = 0; s < 6; ++s) {
+    const gcm::U128 right = shuffle_down(acc, 1 << s), left = gcm::gf128_mul(tree[s], acc);
+    acc = gcm::U128{left.hi ^ right.hi, left.lo ^ right.lo};
+  }
+  if (lane == 0) wave_part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    gcm::U128 y = wave_part[0];
+#pragma unroll 1
+    for (int w = 1; w < 4; ++w) {
+      y = gcm::gf128_mul(tree[6], y);
+      y = gcm::U128{y.hi ^ wave_part[w].hi, y.lo ^ wave_part[w].lo};
+    }
+    part[blockIdx.x] = y;
+  }
+}
+
+// sse_gcm_kernel keeps these steps written out in its body: calling the functions above cost it
+// 30 VGPRs (140 -> 170 in the compiler's table) and with them its third wave per SIMD.
 template <int Q>
 __global__ __launch_bounds__(kCrcWgThreads) void sse_gcm_kernel(SseGcmLaunch a, const DevCrcTables* __restrict__ gt) {
   static_assert(Q >= 0 && Q < 4 && kCrcWgThreads == 256 && gcm::kGcmTileBlocks == 4 * kCrcWgThreads, "tile shape");
@@ -2009,6 +2068,156 @@ __global__ __launch_bounds__(kCrcWgThreads) void sse_gcm_kernel(SseGcmLaunch a, 
     }
     a.part[blockIdx.x] = y;
   }
+}
+
+// ---- K7 read: verify, authenticate, decrypt and deliver a stored SSE-S3 blob in one pass ----
+//
+// The block in HBM is [nonce 12][ciphertext n][tag 16]. One launch checks every 512 B slice of it
+// against the .meta image (as crc_read_copy_kernel does), decrypts the ciphertext with K7's CTR
+// keystream, accumulates K7's GHASH of it, and stores the plaintext, and nothing else, into the
+// reader's registered buffer: the ciphertext crosses no link at all.
+//
+// The two axes. CRC slices, chunks and tiles count from block byte 0; AES blocks from byte 12. The
+// kernel lives on the CRC axis: tile T is block bytes [16 KiB * T, 16 KiB * (T + 1)), thread t of
+// its workgroup owns the 64 B chunk at vectors g = 1024 T + 4t .. g + 3, and workgroups stride
+// over tiles as in K7. AES block i is dword 3 of vector i and dwords 0..2 of vector i + 1, so the
+// thread that owns vector i owns block i: counter, GHASH position and output offset 16i all follow
+// from the vector index, and the 12 bytes between the axes are one fixed 3-dword funnel on the load
+// side (a lane takes three dwords from the lane above; lane 63 loads the vector above its wave,
+// which at wave 3 is the first vector of the next tile). The plaintext block then lies on the
+// aligned grid of `out` and leaves as one 16 B store.
+//   On the GHASH side this is gcm::plan_for of the tiles' whole span, 16 KiB * ntiles: no virtual
+// blocks in front, and `vback` zero blocks behind the message (the tag, the bytes behind the block
+// and the rest of the last tile are masked to zero). Zero blocks at the end do count: the fold
+// comes out as the message's sum times H^vback, which gcm::tag_matches takes into account on the
+// host, where multiplying the other side of the comparison costs less than a right-aligned axis
+// would here (every lane's chunk off the CRC's 64 B grid).
+//
+// CRC. A lane holds chunk `lane` of its wave's 4 KiB whole, the MFMA wants lane (n, h) to hold half
+// h of chunk n and of chunk 32 + n: exchanging dwords k and 8 + k between the half-waves (eight
+// v_permlane32_swap) makes exactly that WaveData, and wave_chunk_crcs returns chunk `lane`'s CRC to
+// the lane that decrypts it. The short tail slice is checked by workgroup 0 from byte loads.
+//
+// Registers: 64 for the CRC basis, 40 for two tiles' vectors, 16 + 16 for states and message, the
+// MFMA accumulators and the GHASH operands do not fit three waves per SIMD; two do, without scratch.
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void sse_read_kernel(
+    SseReadLaunch a, const DevCrcTables* __restrict__ gt) {
+  static_assert(kCrcWgThreads == 256 && gcm::kGcmTileBlocks * 16 == kSlicesPerTile * 512, "a CRC tile is a GCM tile");
+  __shared__ MfmaSliceLds lt;
+  __shared__ uint32_t te0[256];
+  __shared__ uint8_t sbox[256];
+  __shared__ gcm::U128 wave_part[4];
+  __shared__ uint32_t wg_bad;
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int64_t n = static_cast<int64_t>(a.n), size = n + 28, nvec = (size + 15) / 16, s_full = size / 512;
+  const u32x4* src = reinterpret_cast<const u32x4*>(a.src);
+  auto load = [&](int64_t v) {
+    uint4 d = make_uint4(0, 0, 0, 0);
+    if (v < nvec) {  // the vector behind the block's end is never loaded
+      const u32x4 x = __builtin_nontemporal_load(src + v);
+      d = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    return d;
+  };
+  auto first_vector = [&](uint64_t tile) { return static_cast<int64_t>(tile * gcm::kGcmTileBlocks + 4 * threadIdx.x); };
+  auto fetch = [&](uint64_t tile, uint4 (&v)[4], uint4& above) {
+    const int64_t g = first_vector(tile);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = load(g + i);
+    above = lane == 63 ? load(g + 4) : make_uint4(0, 0, 0, 0);
+  };
+
+  uint4 cur[4], cur_above;
+  fetch(blockIdx.x, cur, cur_above);
+  i32x4 A[16];
+  load_basis(reinterpret_cast<const i32x4*>(gt + 1), lane, A);
+  load_lds_image(gt, &lt);
+  sse_load_tables(gt, te0, sbox);
+  if (threadIdx.x == 0) wg_bad = 0xFFFFFFFFu;
+  // the nonce: the block's first three dwords, the same for every lane
+  const uint32_t* head = reinterpret_cast<const uint32_t*>(a.src);
+  const uint32_t n0 = head[0], n1 = head[1], n2 = head[2];
+  if (blockIdx.x == 0 && threadIdx.x < 28)  // nonce and stored tag for the host: block bytes [0, 12) and [12 + n, 28 + n)
+    a.nonce_tag[threadIdx.x] = a.src[threadIdx.x < 12 ? threadIdx.x : n + threadIdx.x];
+  __syncthreads();
+
+  gcm::U128 acc{0, 0};
+  uint32_t bad = 0xFFFFFFFFu;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    uint4 nxt[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+    uint4 nxt_above = make_uint4(0, 0, 0, 0);
+    if (tile + gridDim.x < a.ntiles) fetch(tile + gridDim.x, nxt, nxt_above);
+    const int64_t g = first_vector(tile);
+    const uint32_t d[16] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                            cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+
+    // verify: the lane's chunk, halves exchanged across the half-waves into the MFMA's operand
+    {
+      uint32_t p0[8], p1[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const auto r = __builtin_amdgcn_permlane32_swap(d[k], d[8 + k], false, false);
+        p0[k] = r[0];  // lanes 0..31: own dword k; lanes 32..63: dword 8 + k of lane - 32
+        p1[k] = r[1];  // lanes 0..31: dword k of lane + 32; lanes 32..63: own dword 8 + k
+      }
+      WaveData w;
+      w.v[0] = make_uint4(p0[0], p0[1], p0[2], p0[3]);
+      w.v[1] = make_uint4(p0[4], p0[5], p0[6], p0[7]);
+      w.v[2] = make_uint4(p1[0], p1[1], p1[2], p1[3]);
+      w.v[3] = make_uint4(p1[4], p1[5], p1[6], p1[7]);
+      const uint32_t r = slice_from_chunks(lt, wave_chunk_crcs(A, w, lane), lane);
+      const int64_t i = static_cast<int64_t>(tile) * kSlicesPerTile + wave * 8 + sw;
+      if (i < s_full && sl == 0 && a.meta[i] != __builtin_bswap32(r ^ a.full_init)) bad = min(bad, static_cast<uint32_t>(i));
+    }
+
+    // the ciphertext of blocks g .. g + 3: the lane's dwords from 3 on, then three from above
+    const uint32_t ab[3] = {cur_above.x, cur_above.y, cur_above.z};
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i + 3 < 16) {
+        m[i] = d[i + 3];
+      } else {
+        const uint32_t up = __shfl_down(d[i + 3 - 16], 1);
+        m[i] = lane == 63 ? ab[i + 3 - 16] : up;
+      }
+    }
+
+    uint32_t ks[4][4];
+    sse_keystream(te0, sbox, a.rk, n0, n1, n2, g, ks);
+
+    if (tile != blockIdx.x) acc = gcm::gf128_mul(a.hjump, acc);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t pos = 16 * (g + b);  // of the block in the message and in `out`
+      uint32_t c[4], o[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        c[k] = m[4 * b + k] & sse_keep(n - pos - 4 * k);
+        o[k] = m[4 * b + k] ^ ks[b][k];
+      }
+      acc = ghash_absorb(acc, a.h, c);
+      if (pos + 16 <= n) {
+        *reinterpret_cast<uint4*>(a.out + pos) = make_uint4(o[0], o[1], o[2], o[3]);
+      } else {
+        for (int64_t p = pos; p < n; ++p) a.out[p] = static_cast<uint8_t>(o[(p - pos) >> 2] >> (8 * ((p - pos) & 3)));
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+    cur_above = nxt_above;
+  }
+
+  if (size % 512 && blockIdx.x == 0 && wave == 0) {
+    const uint32_t tail_len = static_cast<uint32_t>(size % 512);
+    const uint32_t r =
+        slice_from_chunks(lt, wave_chunk_crcs(A, load_tail_wave(a.src + s_full * 512, tail_len, lane), lane), lane);
+    if (lane == 0 && a.meta[s_full] != __builtin_bswap32(r ^ a.tail_init)) bad = min(bad, static_cast<uint32_t>(s_full));
+  }
+  if (bad != 0xFFFFFFFFu) atomicMin(&wg_bad, bad);
+  ghash_wg_partial(acc, a.tree, wave_part, a.part);  // its barrier orders wg_bad too
+  if (threadIdx.x == 0) a.part_bad[blockIdx.x] = wg_bad;
 }
 
 }  // namespace
@@ -2520,6 +2729,43 @@ hipError_t launch_sse_gcm(const SseGcmLaunch& a, const DevCrcTables* t, int grid
     case 2: hipLaunchKernelGGL(sse_gcm_kernel<2>, g, b, 0, s, a, t); break;
     default: hipLaunchKernelGGL(sse_gcm_kernel<3>, g, b, 0, s, a, t); break;
   }
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_sse_read_fused{-1};
+
+static std::atomic<int64_t> g_sse_read_min_bytes{-1};
+
+void set_sse_read_fused(bool on, int64_t min_bytes) {
+  g_sse_read_fused.store(on ? 1 : 0);
+  if (min_bytes >= 0) g_sse_read_min_bytes.store(min_bytes);
+}
+
+uint64_t sse_read_fused_min_bytes() {
+  int64_t v = g_sse_read_min_bytes.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_READ_FUSED_MIN_BYTES");
+    g_sse_read_min_bytes.store(v = e && std::atoll(e) >= 0 ? std::atoll(e) : static_cast<int64_t>(kSseReadFusedMinBytes));
+  }
+  return static_cast<uint64_t>(v);
+}
+
+bool sse_read_fused_enabled() {
+  int v = g_sse_read_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_READ_FUSED");
+    g_sse_read_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+hipError_t launch_sse_read(const SseReadLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const gcm::Plan p = gcm::plan_for(kSseReadTileBytes * sse_read_tiles(a.n));
+  if (!t || !a.src || !a.meta || !a.out || !a.part || !a.part_bad || !a.nonce_tag || a.n == 0 ||
+      p.nblocks > 0xFFFFFFFEull || reinterpret_cast<uintptr_t>(a.src) % 16 || reinterpret_cast<uintptr_t>(a.out) % 16 ||
+      reinterpret_cast<uintptr_t>(a.part) % 16 || a.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sse_read_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
   return hipGetLastError();
 }
 

@@ -2202,7 +2202,18 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
   uint64_t got = 0;
   std::string msg;
   FastClient::Times t;
-  if (fc_->read_known(meta, &slot, &got, &msg, &t, r.rid, 0, 0) != FastClient::Ok) return proxy(c, r, nullptr, 0, "read");
+  const uint64_t plen = size - 28;
+  // The whole object wanted: the chunkserver's GPU verifies, authenticates and decrypts the blob where
+  // it is stored and only the plaintext reaches the slot. An authentication failure there is as
+  // final as here; anything else it declines goes on below, unchanged.
+  const FastClient::Status fused =
+      plen && sse_offload() && (!r.get("range") || r.get("range")->empty())
+          ? fc_->sse_read(meta, reinterpret_cast<const uint8_t*>(dk.data()), &slot, &got, r.rid)
+          : FastClient::NotHandled;
+  if (fused == FastClient::Failed) return proxy(c, r, nullptr, 0, "sse");
+  const uint64_t lead = fused == FastClient::Ok ? 0 : 12;  // where the plaintext starts in the slot
+  if (fused != FastClient::Ok && fc_->read_known(meta, &slot, &got, &msg, &t, r.rid, 0, 0) != FastClient::Ok)
+    return proxy(c, r, nullptr, 0, "read");
   struct Release {
     FrontStore* fc;
     int64_t s;
@@ -2210,19 +2221,23 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
       if (s >= 0) fc->release(s);
     }
   } rel{fc_, slot};
-  if (got != size) return proxy(c, r, nullptr, 0, "short-read");
   uint8_t* b = fc_->slot_mut(slot);
-  const uint64_t plen = size - 28;
-  // on the chunkserver's GPU when it takes it; an authentication failure there is as final as here
-  const FastClient::Status off =
-      plen && sse_offload()
-          ? fc_->sse_crypt(slot, 12, plen, reinterpret_cast<const uint8_t*>(dk.data()), b, false, b + 12 + plen, r.rid)
-          : FastClient::NotHandled;
-  if (off == FastClient::Failed) return proxy(c, r, nullptr, 0, "sse");
-  if (off == FastClient::Ok)
+  if (fused == FastClient::Ok) {
+    if (got != plen) return proxy(c, r, nullptr, 0, "short-read");
     st_.sse_offloaded++;
-  else if (!crypto::aes256gcm_decrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), b, b + 12, plen, b + 12 + plen))
-    return proxy(c, r, nullptr, 0, "sse");
+  } else {
+    if (got != size) return proxy(c, r, nullptr, 0, "short-read");
+    // on the chunkserver's GPU when it takes it; an authentication failure there is as final as here
+    const FastClient::Status off =
+        plen && sse_offload()
+            ? fc_->sse_crypt(slot, 12, plen, reinterpret_cast<const uint8_t*>(dk.data()), b, false, b + 12 + plen, r.rid)
+            : FastClient::NotHandled;
+    if (off == FastClient::Failed) return proxy(c, r, nullptr, 0, "sse");
+    if (off == FastClient::Ok)
+      st_.sse_offloaded++;
+    else if (!crypto::aes256gcm_decrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), b, b + 12, plen, b + 12 + plen))
+      return proxy(c, r, nullptr, 0, "sse");
+  }
   uint64_t s = 0, e = 0;
   int rng = parse_range(r.get("range"), plen, &s, &e);
   if (rng >= 2) return proxy(c, r, nullptr, 0, "range");
@@ -2245,7 +2260,7 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
     st_.sse_gets++;
     st_.bytes_out += want;
   }
-  return send_head_body(c->io(), h, b + 12 + from, want);
+  return send_head_body(c->io(), h, b + lead + from, want);
 }
 
 // GET of a completed multipart object: the parts' sizes come from the layout the completion

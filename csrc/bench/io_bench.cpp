@@ -848,6 +848,82 @@ static int sse_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// The range rows of --sse-read: plaintext [n / 2 + 5, + want) of a stored blob by three routes that
+// alternate inside every repetition. [0] staged, as a gateway without the range kernel serves a
+// Range GET: read_into of the whole blob, sse_crypt where it lies, the range sent from where it
+// fell. [1] ChunkStore::sse_read with the range: one sse_read_range_kernel launch. [2] for
+// reference, sse_read of the whole object: one sse_read_kernel launch. Same clock, warm-ups, median
+// and spread as the whole-object rows; `match` compares every call's bytes with the original.
+static int sse_read_range_rows(ChunkStore& s, const uint8_t key[32], const uint8_t nonce[12], int reps) {
+  int rc = 0;
+  for (uint64_t n : {1ull << 20, 16ull << 20, 100ull << 20}) {
+    const auto plain = random_bytes(n, static_cast<uint32_t>(n + 47));
+    std::vector<uint8_t> blob(n + 28);
+    std::memcpy(blob.data(), nonce, 12);
+    std::memcpy(blob.data() + 12, plain.data(), n);
+    crypto::aes256gcm_encrypt_inplace(key, nonce, blob.data() + 12, n, blob.data() + 12 + n);
+    const std::string id = "sse-range-" + std::to_string(n);
+    if (!s.write(id, blob.data(), blob.size(), 0).ok) return 1;
+    uint8_t* out = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void**>(&out), n + 64, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) return 1;
+    s.register_host(out, n + 64);
+    const int iters = static_cast<int>(std::clamp<uint64_t>((64ull << 20) / n, 2, 100));
+    const uint64_t from = n / 2 + 5;
+    for (uint64_t want : {64ull << 10, 1ull << 20, 8ull << 20}) {
+      if (from + want > n) continue;
+      std::vector<double> us[3];
+      bool match = true;
+      auto run = [&](int route, int count) {
+        set_sse_read_fused(route != 0, 0);
+        double t = 0;
+        for (int i = 0; i < count && match; ++i) {
+          std::memset(out, 0, 64);
+          std::string err;
+          uint64_t got = 0;
+          const auto t0 = Clock::now();
+          if (route == 0) {
+            const ReadResult r = s.read_into(id, 0, n + 28, out);
+            const bool ok = r.status == ReadStatus::Ok && s.sse_crypt(out + 12, n, key, out, false, out + 12 + n, &err);
+            t += secs(t0, Clock::now());
+            match = ok && std::memcmp(out + 12 + from, plain.data() + from, want) == 0;
+          } else if (route == 1) {
+            const auto st = s.sse_read(id, key, out + from % 16, want, &got, &err, nullptr, true, from, want);
+            t += secs(t0, Clock::now());
+            match = st == ChunkStore::SseRead::Ok && got == want && std::memcmp(out + from % 16, plain.data() + from, want) == 0;
+          } else {
+            const auto st = s.sse_read(id, key, out, n, &got, &err, nullptr, true);
+            t += secs(t0, Clock::now());
+            match = st == ChunkStore::SseRead::Ok && got == n && std::memcmp(out + from, plain.data() + from, want) == 0;
+          }
+        }
+        return t * 1e6 / count;
+      };
+      for (int route = 0; route < 3; ++route) run(route, 2);
+      const uint64_t before = s.stats().sse_fused_range_reads;
+      for (int rep = 0; rep < reps; ++rep)
+        for (int route = 2; route >= 0; --route) us[route].push_back(run(route, iters));
+      match = match && s.stats().sse_fused_range_reads - before == static_cast<uint64_t>(reps) * iters;
+      auto median = [](std::vector<double> v) {
+        std::sort(v.begin(), v.end());
+        return v[v.size() / 2];
+      };
+      auto spread = [](const std::vector<double>& v) { return *std::max_element(v.begin(), v.end()) - *std::min_element(v.begin(), v.end()); };
+      std::printf("{\"sse_read_range\": {\"bytes\": %llu, \"from\": %llu, \"want\": %llu, \"iters\": %d, "
+                  "\"range_median_us\": %.1f, \"range_spread_us\": %.1f, \"staged_median_us\": %.1f, "
+                  "\"staged_spread_us\": %.1f, \"whole_median_us\": %.1f, \"whole_spread_us\": %.1f, \"match\": %s}}\n",
+                  static_cast<unsigned long long>(n), static_cast<unsigned long long>(from),
+                  static_cast<unsigned long long>(want), iters, median(us[1]), spread(us[1]), median(us[0]), spread(us[0]),
+                  median(us[2]), spread(us[2]), match ? "true" : "false");
+      std::fflush(stdout);
+      if (!match) rc = 1;
+    }
+    s.unregister_host(out);
+    (void)hipHostFree(out);
+    s.remove(id);
+  }
+  return rc;
+}
+
 // --sse-read: ChunkStore::sse_read of a stored blob [nonce 12][ciphertext n][tag 16] into a registered
 // buffer: the one-kernel route against what a caller without it does (read_into of the whole blob,
 // then sse_crypt where the ciphertext lies, under sse_crypt's own floor, the plaintext left at + 12
@@ -933,6 +1009,7 @@ static int sse_read_bench(int device, const std::string& dir, int reps) {
     (void)hipHostFree(out);
     s.remove(id);
   }
+  if (sse_read_range_rows(s, key, nonce, reps) != 0) rc = 1;
   set_sse_read_fused(true, static_cast<int64_t>(kSseReadFusedMinBytes));
   std::filesystem::remove_all(dir);
   return rc;

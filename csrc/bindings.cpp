@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include <chrono>
+#include <optional>
 
 #include "trace.h"
 #include "chunk_store.h"
@@ -553,8 +554,10 @@ PYBIND11_MODULE(_dfs_native, m) {
       }, py::arg("buffer"), py::arg("key"), py::arg("nonce"), py::arg("encrypt"), py::arg("tag") = py::bytes())
       // GET of a stored SSE-S3 blob [nonce][ciphertext][tag]: the plaintext into a writable buffer
       // of at least that many bytes, nothing behind it written. Returns (status, n): 0 Ok, 1 NotFound, 2 Corrupt (n = the
-      // bad slice), 3 AuthFailed, 4 IoError.
-      .def("sse_read", [](ChunkStore& s, const std::string& id, py::bytes key, py::buffer out) {
+      // bad slice), 3 AuthFailed, 4 IoError. With `length`, plaintext [offset, offset + length) alone, at the
+      // buffer's front; the kernel takes a range when the buffer's address % 16 == offset % 16.
+      .def("sse_read", [](ChunkStore& s, const std::string& id, py::bytes key, py::buffer out, uint64_t offset,
+                          std::optional<uint64_t> length) {
         py::buffer_info bi = out.request(true);
         std::string k = key, err;
         if (k.size() != 32) throw std::invalid_argument("sse_read: 32-byte key");
@@ -564,14 +567,15 @@ PYBIND11_MODULE(_dfs_native, m) {
         {
           py::gil_scoped_release rel;
           st = s.sse_read(id, reinterpret_cast<const uint8_t*>(k.data()), static_cast<uint8_t*>(bi.ptr),
-                          static_cast<uint64_t>(bi.size * bi.itemsize), &n, &err, &bad);
+                          static_cast<uint64_t>(bi.size * bi.itemsize), &n, &err, &bad, false, offset,
+                          length ? std::min<uint64_t>(*length, UINT64_MAX - 1) : UINT64_MAX);
         }
         gcm::wipe(&k[0], k.size());
         return py::make_tuple(static_cast<int>(st), st == ChunkStore::SseRead::Corrupt ? static_cast<uint64_t>(bad) : n);
-      }, py::arg("block_id"), py::arg("key"), py::arg("out_buffer"))
-      .def("sse_read_fusable", [](ChunkStore& s, const std::string& id, py::buffer out) {
-        return s.sse_read_fusable(id, static_cast<const uint8_t*>(out.request().ptr));
-      })
+      }, py::arg("block_id"), py::arg("key"), py::arg("out_buffer"), py::arg("offset") = 0, py::arg("length") = py::none())
+      .def("sse_read_fusable", [](ChunkStore& s, const std::string& id, py::buffer out, uint64_t offset) {
+        return s.sse_read_fusable(id, static_cast<const uint8_t*>(out.request().ptr), offset);
+      }, py::arg("block_id"), py::arg("out_buffer"), py::arg("offset") = 0)
       // degraded read: bytes [offset, offset + length) of the RS(k, m) file whose k + m shards are
       // the resident blocks `block_ids` ("" = lost) into `out`; a registered `out` takes the
       // single-kernel path. Returns the number of bytes placed, None on failure.

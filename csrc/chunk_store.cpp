@@ -2564,6 +2564,7 @@ StoreStats ChunkStore::stats() {
   s.ec_fused_reads = ec_fused_reads_.load();
   s.sse_fused_crypts = sse_fused_crypts_.load();
   s.sse_fused_reads = sse_fused_reads_.load();
+  s.sse_fused_range_reads = sse_fused_range_reads_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -4163,33 +4164,40 @@ constexpr uint64_t kSseReadNonceTagOff = kSseReadBadOff + gcm::kGcmMaxGrid * siz
 constexpr uint64_t kSseReadScratch = kSseReadNonceTagOff + 32;
 }  // namespace
 
-// The block pinned in HBM when sse_read_kernel would take it into `out` (the caller unpins), else null.
-const uint8_t* ChunkStore::sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size) {
-  if (!gpu() || !sse_read_fused_enabled() || !crc_mfma_enabled() || reinterpret_cast<uintptr_t>(out) % 16) return nullptr;
+// The block pinned in HBM when sse_read_kernel, or for a range sse_read_range_kernel, would take it
+// into `out` (the caller unpins), else null. want == UINT64_MAX: up to the plaintext's end.
+const uint8_t* ChunkStore::sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size, uint64_t from,
+                                        uint64_t want) {
+  if (!gpu() || !sse_read_fused_enabled() || !crc_mfma_enabled() || (reinterpret_cast<uintptr_t>(out) - from) % 16)
+    return nullptr;
   HIP_OK(hipSetDevice(cfg_.device));
   const uint8_t* d = pin_device(id, size);
   if (!d) return nullptr;
   if (*size >= 29 && *size - 28 >= sse_read_fused_min_bytes() && sse_read_tiles(*size - 28) <= (0xFFFFFFFEull >> 10) &&
-      device_view(out, *size - 28) != nullptr)
-    return d;
+      from < *size - 28) {
+    const uint64_t left = *size - 28 - from;
+    if (want == UINT64_MAX) want = left;
+    if (want != 0 && want <= left && device_view(out, want) != nullptr) return d;
+  }
   unpin(id);
   return nullptr;
 }
 
-bool ChunkStore::sse_read_fusable(const std::string& id, const uint8_t* out) {
+bool ChunkStore::sse_read_fusable(const std::string& id, const uint8_t* out, uint64_t from, uint64_t want) {
   uint64_t size = 0;
-  if (!sse_read_pin(id, out, &size)) return false;
+  if (!sse_read_pin(id, out, &size, from, want)) return false;
   unpin(id);
   return true;
 }
 
 ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t key[32], uint8_t* out, uint64_t out_cap,
-                                         uint64_t* n_out, std::string* err, int64_t* bad_slice, bool fused_only) {
+                                         uint64_t* n_out, std::string* err, int64_t* bad_slice, bool fused_only,
+                                         uint64_t from, uint64_t want) {
   TraceRange tr("dfs.store.sse_read");  // no key material in ranges, logs or errors
   *n_out = 0;
   if (bad_slice) *bad_slice = -1;
   uint64_t size = 0;
-  const uint8_t* d = sse_read_pin(id, out, &size);
+  const uint8_t* d = sse_read_pin(id, out, &size, from, want);
   if (!d) {
     const int64_t have = block_size(id);
     if (have < 0) {
@@ -4198,15 +4206,28 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
     }
     size = static_cast<uint64_t>(have);
   }
-  if (size < 29 || size - 28 > out_cap) {
+  if (size < 29) {
     if (d) unpin(id);
-    *err = size < 29 ? "not an SSE blob: " + std::to_string(size) + " bytes"
-                     : "buffer of " + std::to_string(out_cap) + " bytes for " + std::to_string(size - 28) + " of plaintext";
+    *err = "not an SSE blob: " + std::to_string(size) + " bytes";
     return SseRead::IoError;
   }
+  const uint64_t n = size - 28;
+  if (want == UINT64_MAX && from <= n) want = n - from;
+  if (want == 0 || from > n || want > n - from) {
+    if (d) unpin(id);
+    *err = "range [" + std::to_string(from) + ", +" + std::to_string(want) + ") outside the " + std::to_string(n) +
+           " bytes of plaintext";
+    return SseRead::IoError;
+  }
+  if (want > out_cap) {
+    if (d) unpin(id);
+    *err = "buffer of " + std::to_string(out_cap) + " bytes for " + std::to_string(want) + " of plaintext";
+    return SseRead::IoError;
+  }
+  const bool whole = from == 0 && want == n;
   if (d) {
-    uint8_t* dout = device_view(out, size - 28);
-    const uint64_t n = size - 28, ntiles = sse_read_tiles(n);
+    uint8_t* dout = device_view(out, want);
+    const uint64_t ntiles = sse_read_tiles(n);
     const gcm::Plan plan = gcm::plan_for(kSseReadTileBytes * ntiles);
     Lane* l = acquire_lane();
     ensure_hscratch(l, kSseReadScratch);
@@ -4214,7 +4235,8 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
     // and the powers of H that the store owns is wiped on each way out. A launch that fails has
     // written nothing, so the call goes on to the staged route; a failed synchronise is an error.
     gcm::Keys keys;
-    SseReadLaunch a{};
+    SseReadRangeLaunch ra{};
+    SseReadLaunch& a = ra.r;
     hipError_t launched = hipErrorNotReady, synced = hipSuccess;
     uint32_t bad = 0xFFFFFFFFu;
     bool authentic = false;
@@ -4234,7 +4256,11 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
       a.part = reinterpret_cast<gcm::U128*>(hdev);
       a.part_bad = reinterpret_cast<uint32_t*>(hdev + kSseReadBadOff);
       a.nonce_tag = hdev + kSseReadNonceTagOff;
-      launched = launch_sse_read(a, dtables_, plan.grid, l->stream);
+      ra.from = from;
+      ra.want = want;
+      // the whole object stays with sse_read_kernel; a range authenticates all and decrypts its tiles
+      launched = whole ? launch_sse_read(a, dtables_, plan.grid, l->stream)
+                       : launch_sse_read_range(ra, dtables_, plan.grid, l->stream);
       if (launched == hipSuccess) {
         launches_++;
         synced = hipStreamSynchronize(l->stream);
@@ -4250,7 +4276,7 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
         gcm::wipe(l->hscratch, plan.grid * sizeof(gcm::U128));
       }
     }
-    gcm::wipe(&a, sizeof(a));
+    gcm::wipe(&ra, sizeof(ra));
     gcm::wipe(&keys, sizeof(keys));
     release_lane(l);
     unpin(id);
@@ -4260,11 +4286,12 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
         return SseRead::IoError;
       }
       sse_fused_reads_++;
+      if (!whole) sse_fused_range_reads_++;
       if (authentic) {
-        *n_out = n;
+        *n_out = want;
         return SseRead::Ok;
       }
-      std::memset(out, 0, n);  // plaintext of a blob that did not verify is nobody's
+      std::memset(out, 0, want);  // plaintext of a blob that did not verify is nobody's
       if (bad != 0xFFFFFFFFu) {
         std::lock_guard<std::mutex> g(mu_);
         ++st_.crc_mismatches;
@@ -4283,27 +4310,31 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
   }
   // staged: the ciphertext straight to out[0, n), nonce and tag beside it on the stack, then
   // sse_crypt where the ciphertext lies. The three ranges touch every slice of the blob between
-  // them, so a bad slice anywhere is found; no byte of `out` behind n is written.
-  const uint64_t n = size - 28;
+  // them, so a bad slice anywhere is found; no byte of `out` behind n is written. A range takes
+  // the same steps in a temporary of the blob's size (GCM authenticates all or nothing) and
+  // copies its bytes out.
+  std::vector<uint8_t> tmp(whole ? 0 : n);
+  uint8_t* pt = whole ? out : tmp.data();
   uint8_t nonce_tag[28];
   const struct {
     uint64_t off, len;
     uint8_t* to;
-  } parts[3] = {{12, n, out}, {0, 12, nonce_tag}, {12 + n, 16, nonce_tag + 12}};
+  } parts[3] = {{12, n, pt}, {0, 12, nonce_tag}, {12 + n, 16, nonce_tag + 12}};
   for (const auto& p : parts) {
     const ReadResult r = read_into(id, p.off, p.len, p.to);
     if (r.status == ReadStatus::Ok && !r.partial_corrupt) continue;
-    std::memset(out, 0, n);
+    std::memset(out, 0, want);
     *err = r.error;
     if (bad_slice) *bad_slice = r.bad_slice;
     return r.status == ReadStatus::NotFound ? SseRead::NotFound
            : r.status == ReadStatus::Corrupt || r.partial_corrupt ? SseRead::Corrupt : SseRead::IoError;
   }
-  if (!sse_crypt(out, n, key, nonce_tag, false, nonce_tag + 12, err)) {
-    std::memset(out, 0, n);
+  if (!sse_crypt(pt, n, key, nonce_tag, false, nonce_tag + 12, err)) {
+    std::memset(out, 0, want);
     return *err == kSseAuthFailed ? SseRead::AuthFailed : SseRead::IoError;
   }
-  *n_out = n;
+  if (!whole) std::memcpy(out, pt + from, want);
+  *n_out = want;
   return SseRead::Ok;
 }
 

@@ -97,6 +97,7 @@ struct StoreStats {
   uint64_t ec_fused_reads = 0;    // degraded EC range reads served by one ec_read_kernel launch
   uint64_t sse_fused_crypts = 0;  // SSE bodies encrypted or decrypted by one sse_gcm_kernel launch
   uint64_t sse_fused_reads = 0;   // stored SSE blobs verified, decrypted and delivered by one sse_read_kernel launch
+  uint64_t sse_fused_range_reads = 0;  // of those, byte ranges by sse_read_range_kernel
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -335,10 +336,19 @@ class ChunkStore {
   // crc_mismatches, AuthFailed has *err = kSseAuthFailed, and both leave out[0, n) zeroed. With
   // fused_only the call answers Declined instead of taking the staged route (the fast path, whose
   // caller then reads its own way). The key schedule and the powers of H are wiped before this returns.
+  //   A Range GET: with `want` given, out[0, want) receives plaintext [from, from + want), *n = want,
+  // out_cap >= want, and nothing outside is written; want == UINT64_MAX is "to the end". want == 0
+  // or from + want > n is IoError. The kernel route needs out % 16 == from % 16 instead of an
+  // aligned `out`, and its floor still applies to the blob's n: one sse_read_range_kernel launch
+  // verifies and authenticates the whole blob and decrypts only the range's tiles (from == 0 and
+  // want == n launches sse_read_kernel). Staged, the blob is read and decrypted into a temporary and
+  // the range copied. Corrupt and AuthFailed leave out[0, want) zeroed wherever the fault lies.
   enum class SseRead : int { Ok = 0, NotFound = 1, Corrupt = 2, AuthFailed = 3, IoError = 4, Declined = 5 };
-  bool sse_read_fusable(const std::string& id, const uint8_t* out);  // would sse_read take the kernel
+  bool sse_read_fusable(const std::string& id, const uint8_t* out, uint64_t from = 0,
+                        uint64_t want = UINT64_MAX);  // would sse_read take the kernel
   SseRead sse_read(const std::string& id, const uint8_t key[32], uint8_t* out, uint64_t out_cap, uint64_t* n,
-                   std::string* err, int64_t* bad_slice = nullptr, bool fused_only = false);
+                   std::string* err, int64_t* bad_slice = nullptr, bool fused_only = false, uint64_t from = 0,
+                   uint64_t want = UINT64_MAX);
   // Device bytes into host memory (registered: one DMA) and synchronously complete.
   bool device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n);
   // A copy of device bytes committed as block `id` (checksummed, verified, made durable).
@@ -541,9 +551,9 @@ class ChunkStore {
   // block of n bytes.
   bool ec_fused(Lane* l, EcFusedLaunch& a, const std::vector<std::vector<uint8_t>>& mat, uint64_t len,
                 std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
-  const uint8_t* sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size);
+  const uint8_t* sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size, uint64_t from, uint64_t want);
   std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0},
-      sse_fused_crypts_{0}, sse_fused_reads_{0};
+      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

@@ -805,13 +805,16 @@ FastClient::Status FastClient::sse_crypt(uint64_t off, uint64_t n, const uint8_t
 }
 
 FastClient::Status FastClient::sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
-                                        const std::string& rid_in) {
+                                        const std::string& rid_in, uint64_t from, uint64_t want, uint64_t* lead) {
   const std::string rid = rid_in.empty() ? new_request_id() : rid_in;
   RequestScope rs(rid);
   if (!base_) return NotHandled;
   pb::FileMetadata m;
   if (!m.decode(meta_pb) || m.blocks.size() != 1 || m.blocks[0].ec_data_shards > 0 || m.size < 29 || m.size > slot_bytes_)
     return NotHandled;
+  const bool ranged = want != UINT64_MAX;
+  if (ranged && (want == 0 || from > m.size - 28 || want > m.size - 28 - from)) return NotHandled;
+  if (lead) *lead = ranged ? from % 16 : 0;
   const pb::BlockInfo& b = m.blocks[0];
   bool local = false;
   for (auto& l : b.locations) local |= strip_scheme(l) == local_cs_;
@@ -821,6 +824,10 @@ FastClient::Status FastClient::sse_read(const std::string& meta_pb, const uint8_
   std::string body;
   put<uint64_t>(body, static_cast<uint64_t>(s));
   put<uint64_t>(body, slot_bytes_);
+  if (ranged) {
+    put<uint64_t>(body, from);
+    put<uint64_t>(body, want);
+  }
   put_str(body, b.block_id);
   put_str(body, std::string(reinterpret_cast<const char*>(key), 32));
   put_str(body, arena_path_);
@@ -828,9 +835,9 @@ FastClient::Status FastClient::sse_read(const std::string& meta_pb, const uint8_
   uint8_t st = 0;
   uint64_t total = 0, got = 0;
   std::string fmsg;
-  const bool sent = fp_call(11, body, &st, &total, &got, &fmsg);
+  const bool sent = fp_call(ranged ? 12 : 11, body, &st, &total, &got, &fmsg);
   gcm::wipe(&body[0], body.size());
-  if (!sent || st != 0 || got + 28 != m.size) {
+  if (!sent || st != 0 || (ranged ? got != want || total != m.size : got + 28 != m.size)) {
     release(s);
     return sent && st == 9 ? Failed : NotHandled;  // FpStatus::AuthFailed is final; anything else is the caller's own read
   }

@@ -136,8 +136,11 @@ class FastClient {
   // GET of the stored SSE-S3 blob that `meta_pb` describes (one block on the co-located chunkserver)
   // by fast-path op 11: verified, authenticated and decrypted by one kernel there, the n plaintext
   // bytes at the front of *slot (the caller releases it). Failed: the tag does not match, which is
-  // final. NotHandled: no slot is held and the caller reads and decrypts as before.
-  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid);
+  // final. NotHandled: no slot is held and the caller reads and decrypts as before. With `want`
+  // given, op 12: plaintext [from, from + want) alone, *n = want, its first byte *lead = from % 16
+  // bytes into the slot (0 for the whole object).
+  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
+                  uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr);
   uint64_t sse_gpu_ops() const { return sse_gpu_.load(); }
   uint64_t ec_gpu_ops() const { return ec_gpu_.load(); }
   uint64_t ec_cpu_ops() const { return ec_cpu_.load(); }

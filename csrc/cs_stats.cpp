@@ -42,6 +42,7 @@ Json stats_json(const StoreStats& t) {
   d.set("ec_fused_reads", t.ec_fused_reads);
   d.set("sse_fused_crypts", t.sse_fused_crypts);
   d.set("sse_fused_reads", t.sse_fused_reads);
+  d.set("sse_fused_range_reads", t.sse_fused_range_reads);
   d.set("pulled_recvs", t.pulled_recvs);
   d.set("pulled_host_appends", t.pulled_host_appends);
   d.set("sliced_stages", t.sliced_stages);

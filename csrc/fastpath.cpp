@@ -973,8 +973,11 @@ void FastPathServer::serve(int fd) {
       }
       gcm::wipe(&key[0], key.size());
       gcm::wipe(body.data(), body.size());
-    } else if (op == 11) {  // SSE_READ: a stored SSE-S3 blob verified, decrypted and delivered by one kernel
+    } else if (op == 11 || op == 12) {  // SSE_READ[_RANGE]: a stored SSE-S3 blob verified, decrypted and delivered by one kernel
       const uint64_t off = rd.get<uint64_t>(), cap = rd.get<uint64_t>();
+      // op 12: the plaintext range [from, from + want), which lands from % 16 bytes into the slot
+      const uint64_t from = op == 12 ? rd.get<uint64_t>() : 0, want = op == 12 ? rd.get<uint64_t>() : UINT64_MAX;
+      const uint64_t lead = from % 16;
       std::string id = rd.str(), key = rd.str(), path = rd.str();
       std::string rid = rd.p < rd.end ? rd.str() : std::string();
       RequestScope rs(rid);
@@ -982,7 +985,8 @@ void FastPathServer::serve(int fd) {
       TraceRange tr("dfs.fp.sse_read");  // the key stays out of ranges, logs and answers
       std::string err;
       uint8_t* base = nullptr;
-      if (!rd.ok || id.empty() || key.size() != 32 || cap == 0 || cap > kMaxTransfer || off > (1ull << 62)) {
+      if (!rd.ok || id.empty() || key.size() != 32 || cap == 0 || cap > kMaxTransfer || off > (1ull << 62) || want == 0 ||
+          cap <= lead) {
         sent = send_response(fd, FpStatus::BadRequest, 0, 0, "malformed sse read request");
       } else if ((base = map_shm(path, off, cap, &err)) == nullptr) {
         sent = send_response(fd, FpStatus::Unsupported, 0, 0, "short-circuit unavailable: " + err);
@@ -994,10 +998,11 @@ void FastPathServer::serve(int fd) {
         uint64_t n = 0;
         int64_t bad = -1;
         // the kernel or nothing: one residency check and one pin, inside the call
-        switch (store_->sse_read(id, reinterpret_cast<const uint8_t*>(key.data()), base + off, cap, &n, &err, &bad, true)) {
+        switch (store_->sse_read(id, reinterpret_cast<const uint8_t*>(key.data()), base + off + lead, cap - lead, &n, &err,
+                                 &bad, true, from, want)) {
           case ChunkStore::SseRead::Ok:
             bump(&FpStats::sse_reads);
-            sent = send_response(fd, FpStatus::Ok, n + 28, n, "");
+            sent = send_response(fd, FpStatus::Ok, op == 12 ? static_cast<uint64_t>(store_->block_size(id)) : n + 28, n, "");
             break;
           case ChunkStore::SseRead::NotFound: sent = send_response(fd, FpStatus::NotFound, 0, 0, err); break;
           case ChunkStore::SseRead::Corrupt: sent = send_response(fd, FpStatus::Corrupt, 0, 0, err); break;

@@ -47,6 +47,11 @@
 //               total = the blob's size and bytes = n, NotFound, Corrupt, AuthFailed, or Unsupported when
 //               ChunkStore::sse_read_fusable says the kernel would not take it: the client then reads and
 //               decrypts its own way. The key crosses only this peer-checked abstract socket.
+//     op 12 SSE_READ_RANGE: u64 shm_off | u64 cap | u64 from | u64 want | u16 id | u16 key(32) | u16 path [| u16 rid]
+//               -- Range GET of the same blob by sse_read_range_kernel: the whole blob verified and
+//               authenticated, plaintext [from, from + want) alone decrypted and stored at shm_off + from % 16
+//               of the client's slot (cap counts from shm_off); answers as op 11 with bytes = want and
+//               total = the blob's size. want == 0 is BadRequest; a range past the plaintext's end IoError.
 //   response = u32 body_len | u8 status | u64 total | u64 bytes | u16 msg_len msg
 //   (for WRITE/REPL ``bytes`` carries replicas_written; for CTRL ``msg`` is the engine reply)
 //

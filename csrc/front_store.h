@@ -75,10 +75,12 @@ class FrontStore {
     return FastClient::NotHandled;
   }
   // GET of a stored SSE-S3 blob decrypted where it is stored (FastClient::sse_read): Ok leaves the
-  // plaintext at the front of *slot. NotHandled, the default: the caller reads and decrypts itself.
+  // plaintext at the front of *slot, or with `want` given plaintext [from, from + want) alone, *lead
+  // bytes into it. NotHandled, the default: the caller reads and decrypts itself.
   virtual Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
-                          const std::string& rid) {
-    (void)meta_pb, (void)key, (void)slot, (void)n, (void)rid;
+                          const std::string& rid, uint64_t from = 0, uint64_t want = UINT64_MAX,
+                          uint64_t* lead = nullptr) {
+    (void)meta_pb, (void)key, (void)slot, (void)n, (void)rid, (void)from, (void)want, (void)lead;
     return FastClient::NotHandled;
   }
   // calls a first-choice path declined and a second one served (LocalFirstFrontStore)
@@ -124,9 +126,9 @@ class FastFrontStore final : public FrontStore {
                    uint8_t tag[16], const std::string& rid) override {
     return slot < 0 ? FastClient::NotHandled : fc_->sse_crypt(static_cast<uint64_t>(slot) + off, n, key, nonce, encrypt, tag, rid);
   }
-  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
-                  const std::string& rid) override {
-    return fc_->sse_read(meta_pb, key, slot, n, rid);
+  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
+                  uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr) override {
+    return fc_->sse_read(meta_pb, key, slot, n, rid, from, want, lead);
   }
 
  private:
@@ -205,9 +207,9 @@ class LocalFirstFrontStore final : public FrontStore {
                    uint8_t tag[16], const std::string& rid) override {
     return slot < 0 ? FastClient::NotHandled : fc_->sse_crypt(static_cast<uint64_t>(slot) + off, n, key, nonce, encrypt, tag, rid);
   }
-  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n,
-                  const std::string& rid) override {
-    return fc_->sse_read(meta_pb, key, slot, n, rid);
+  Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
+                  uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr) override {
+    return fc_->sse_read(meta_pb, key, slot, n, rid, from, want, lead);
   }
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid) override {
     if (fc_->list_components(prefix, out, rid) == FastClient::Ok) return FastClient::Ok;

@@ -20,6 +20,9 @@
 //   K7 read  sse_read_kernel: a GET of an SSE-S3 object in one pass over its stored blob in HBM —
 //          the slices verified on the matrix cores, the ciphertext authenticated and decrypted in
 //          registers, and only the plaintext stored over PCIe into the reader's registered buffer.
+//   K7 range read  sse_read_range_kernel: a Range GET of an SSE-S3 object — every tile of the blob
+//          verified and authenticated as above, the CTR keystream computed and the plaintext stored
+//          only for the tiles that hold bytes of the range.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -319,6 +322,18 @@ bool sse_read_fused_enabled();
 uint64_t sse_read_fused_min_bytes();
 void set_sse_read_fused(bool on, int64_t min_bytes = -1);
 hipError_t launch_sse_read(const SseReadLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// K7 range read (sse_read_range_kernel): plaintext [from, from + want) of the same blob, 0 < want and
+// from + want <= r.n. Everything of SseReadLaunch holds as above (the whole blob is verified and
+// authenticated: same plan, partials, verdicts and host half), except `r.out`: it is the device view
+// of where plaintext byte `from` goes, with r.out % 16 == from % 16, and exactly [r.out, r.out + want)
+// is written. Only the tiles that hold bytes of the range run AES. The floor is that of the whole
+// read and applies to the blob's n, not to want: the pass covers the whole blob (profiles/r12).
+struct SseReadRangeLaunch {
+  SseReadLaunch r;
+  uint64_t from, want;
+};
+hipError_t launch_sse_read_range(const SseReadRangeLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

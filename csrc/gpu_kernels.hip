@@ -2220,6 +2220,162 @@ __global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2
   if (threadIdx.x == 0) a.part_bad[blockIdx.x] = wg_bad;
 }
 
+// ---- K7 range read: authenticate the whole stored blob, decrypt and deliver only a byte range ----
+//
+// sse_read_kernel's axes, loads, CRC and GHASH plan, tile for tile: GCM's tag covers the whole
+// ciphertext and .meta every slice, so every tile of the blob is verified and absorbed, from HBM.
+// CTR's keystream is random access (block i is E_K(nonce || i + 2)), so AES runs only where
+// plaintext leaves, and only plaintext [from, from + want) crosses the link, to out[0, want).
+//
+// A tile holds message bytes [16 KiB * T, 16 KiB * (T + 1)). Against the range it is, for the whole
+// workgroup alike,
+//   outside: CRC and GHASH, then on to the next tile: no keystream, no store;
+//   inside:  every lane's four blocks decrypted and stored whole, as in sse_read_kernel;
+//   edge:    (the range's first or last byte lies in it) a lane whose 64 B miss the range skips the
+//            keystream; of the others' blocks those wholly in range leave as 16 B stores, and the
+//            blocks holding byte `from` and byte `from + want - 1` as byte stores clipped to it.
+// With out % 16 == from % 16, block `pos` goes to out + (pos - from) on out's 16 B grid, so the load
+// side's funnel is the fixed one. In-range tiles are contiguous and workgroups stride over tiles,
+// so the keystream work spreads over min(tiles in range, grid) workgroups without a schedule.
+//
+// The GHASH of a tile is done before its keystream: the accumulate needs the ciphertext alone, and
+// the four AES states are then live only with the message, not with the multiply's operands.
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void sse_read_range_kernel(
+    SseReadRangeLaunch ar, const DevCrcTables* __restrict__ gt) {
+  __shared__ MfmaSliceLds lt;
+  __shared__ uint32_t te0[256];
+  __shared__ uint8_t sbox[256];
+  __shared__ gcm::U128 wave_part[4];
+  __shared__ uint32_t wg_bad;
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const SseReadLaunch& a = ar.r;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int64_t n = static_cast<int64_t>(a.n), size = n + 28, nvec = (size + 15) / 16, s_full = size / 512;
+  const int64_t from = static_cast<int64_t>(ar.from), to = from + static_cast<int64_t>(ar.want);
+  const u32x4* src = reinterpret_cast<const u32x4*>(a.src);
+  auto load = [&](int64_t v) {
+    uint4 d = make_uint4(0, 0, 0, 0);
+    if (v < nvec) {  // the vector behind the block's end is never loaded
+      const u32x4 x = __builtin_nontemporal_load(src + v);
+      d = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    return d;
+  };
+  auto first_vector = [&](uint64_t tile) { return static_cast<int64_t>(tile * gcm::kGcmTileBlocks + 4 * threadIdx.x); };
+  auto fetch = [&](uint64_t tile, uint4 (&v)[4], uint4& above) {
+    const int64_t g = first_vector(tile);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = load(g + i);
+    above = lane == 63 ? load(g + 4) : make_uint4(0, 0, 0, 0);
+  };
+
+  uint4 cur[4], cur_above;
+  fetch(blockIdx.x, cur, cur_above);
+  i32x4 A[16];
+  load_basis(reinterpret_cast<const i32x4*>(gt + 1), lane, A);
+  load_lds_image(gt, &lt);
+  sse_load_tables(gt, te0, sbox);
+  if (threadIdx.x == 0) wg_bad = 0xFFFFFFFFu;
+  const uint32_t* head = reinterpret_cast<const uint32_t*>(a.src);
+  const uint32_t n0 = head[0], n1 = head[1], n2 = head[2];
+  if (blockIdx.x == 0 && threadIdx.x < 28) a.nonce_tag[threadIdx.x] = a.src[threadIdx.x < 12 ? threadIdx.x : n + threadIdx.x];
+  __syncthreads();
+
+  gcm::U128 acc{0, 0};
+  uint32_t bad = 0xFFFFFFFFu;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    uint4 nxt[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+    uint4 nxt_above = make_uint4(0, 0, 0, 0);
+    if (tile + gridDim.x < a.ntiles) fetch(tile + gridDim.x, nxt, nxt_above);
+    const int64_t g = first_vector(tile);
+    const uint32_t d[16] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                            cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+
+    // verify, as sse_read_kernel
+    {
+      uint32_t p0[8], p1[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const auto r = __builtin_amdgcn_permlane32_swap(d[k], d[8 + k], false, false);
+        p0[k] = r[0];
+        p1[k] = r[1];
+      }
+      WaveData w;
+      w.v[0] = make_uint4(p0[0], p0[1], p0[2], p0[3]);
+      w.v[1] = make_uint4(p0[4], p0[5], p0[6], p0[7]);
+      w.v[2] = make_uint4(p1[0], p1[1], p1[2], p1[3]);
+      w.v[3] = make_uint4(p1[4], p1[5], p1[6], p1[7]);
+      const uint32_t r = slice_from_chunks(lt, wave_chunk_crcs(A, w, lane), lane);
+      const int64_t i = static_cast<int64_t>(tile) * kSlicesPerTile + wave * 8 + sw;
+      if (i < s_full && sl == 0 && a.meta[i] != __builtin_bswap32(r ^ a.full_init)) bad = min(bad, static_cast<uint32_t>(i));
+    }
+
+    // the ciphertext of blocks g .. g + 3: the lane's dwords from 3 on, then three from above
+    const uint32_t ab[3] = {cur_above.x, cur_above.y, cur_above.z};
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i + 3 < 16) {
+        m[i] = d[i + 3];
+      } else {
+        const uint32_t up = __shfl_down(d[i + 3 - 16], 1);
+        m[i] = lane == 63 ? ab[i + 3 - 16] : up;
+      }
+    }
+
+    // authenticate: every tile, whatever its class
+    if (tile != blockIdx.x) acc = gcm::gf128_mul(a.hjump, acc);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      uint32_t c[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[k] = m[4 * b + k] & sse_keep(n - 16 * (g + b) - 4 * k);
+      acc = ghash_absorb(acc, a.h, c);
+    }
+
+    // decrypt and deliver: by the tile's class, the same for the whole workgroup
+    const int64_t t_lo = static_cast<int64_t>(tile * kSseReadTileBytes), t_hi = t_lo + static_cast<int64_t>(kSseReadTileBytes);
+    const bool outside = t_hi <= from || t_lo >= to, inside = t_lo >= from && t_hi <= to;
+    if (!outside && (inside || (16 * g < to && 16 * (g + 4) > from))) {
+      uint32_t ks[4][4];
+      sse_keystream(te0, sbox, a.rk, n0, n1, n2, g, ks);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int64_t pos = 16 * (g + b);  // of the block in the message; out holds byte `from` first
+        uint32_t o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = m[4 * b + k] ^ ks[b][k];
+        uint8_t* dst = a.out + (pos - from);
+        if (inside || (pos >= from && pos + 16 <= to)) {
+          *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else if (pos < to && pos + 16 > from) {  // the block of the range's first or last byte
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int64_t p = pos + 4 * k + i;
+              if (p >= from && p < to) dst[4 * k + i] = static_cast<uint8_t>(o[k] >> (8 * i));
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+    cur_above = nxt_above;
+  }
+
+  if (size % 512 && blockIdx.x == 0 && wave == 0) {
+    const uint32_t tail_len = static_cast<uint32_t>(size % 512);
+    const uint32_t r =
+        slice_from_chunks(lt, wave_chunk_crcs(A, load_tail_wave(a.src + s_full * 512, tail_len, lane), lane), lane);
+    if (lane == 0 && a.meta[s_full] != __builtin_bswap32(r ^ a.tail_init)) bad = min(bad, static_cast<uint32_t>(s_full));
+  }
+  if (bad != 0xFFFFFFFFu) atomicMin(&wg_bad, bad);
+  ghash_wg_partial(acc, a.tree, wave_part, a.part);  // its barrier orders wg_bad too
+  if (threadIdx.x == 0) a.part_bad[blockIdx.x] = wg_bad;
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -2766,6 +2922,18 @@ hipError_t launch_sse_read(const SseReadLaunch& a, const DevCrcTables* t, int gr
       reinterpret_cast<uintptr_t>(a.part) % 16 || a.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(sse_read_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_sse_read_range(const SseReadRangeLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const SseReadLaunch& r = a.r;
+  const gcm::Plan p = gcm::plan_for(kSseReadTileBytes * sse_read_tiles(r.n));
+  if (!t || !r.src || !r.meta || !r.out || !r.part || !r.part_bad || !r.nonce_tag || r.n == 0 || a.want == 0 ||
+      a.from > r.n || a.want > r.n - a.from || p.nblocks > 0xFFFFFFFEull || reinterpret_cast<uintptr_t>(r.src) % 16 ||
+      (reinterpret_cast<uintptr_t>(r.out) - a.from) % 16 || reinterpret_cast<uintptr_t>(r.part) % 16 ||
+      r.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sse_read_range_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
   return hipGetLastError();
 }
 

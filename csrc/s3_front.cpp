@@ -2203,15 +2203,22 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
   std::string msg;
   FastClient::Times t;
   const uint64_t plen = size - 28;
-  // The whole object wanted: the chunkserver's GPU verifies, authenticates and decrypts the blob where
-  // it is stored and only the plaintext reaches the slot. An authentication failure there is as
-  // final as here; anything else it declines goes on below, unchanged.
+  uint64_t s = 0, e = 0;
+  const int rng = parse_range(r.get("range"), plen, &s, &e);
+  // The whole object or one satisfiable range wanted: the chunkserver's GPU verifies and authenticates
+  // the blob where it is stored, decrypts what is wanted of it, and only that plaintext reaches the
+  // slot. An authentication failure there is as final as here; anything else it declines, and every
+  // other Range header, goes on below, unchanged.
+  uint64_t at = 0;  // of the wanted plaintext in the slot, when the kernel delivered just a range
   const FastClient::Status fused =
-      plen && sse_offload() && (!r.get("range") || r.get("range")->empty())
+      !plen || !sse_offload() ? FastClient::NotHandled
+      : rng == 1 ? fc_->sse_read(meta, reinterpret_cast<const uint8_t*>(dk.data()), &slot, &got, r.rid, s, e - s + 1, &at)
+      : !r.get("range") || r.get("range")->empty()
           ? fc_->sse_read(meta, reinterpret_cast<const uint8_t*>(dk.data()), &slot, &got, r.rid)
           : FastClient::NotHandled;
   if (fused == FastClient::Failed) return proxy(c, r, nullptr, 0, "sse");
-  const uint64_t lead = fused == FastClient::Ok ? 0 : 12;  // where the plaintext starts in the slot
+  const bool ranged = fused == FastClient::Ok && rng == 1;  // the slot holds the range alone
+  const uint64_t lead = fused == FastClient::Ok ? at : 12;  // where the plaintext starts in the slot
   if (fused != FastClient::Ok && fc_->read_known(meta, &slot, &got, &msg, &t, r.rid, 0, 0) != FastClient::Ok)
     return proxy(c, r, nullptr, 0, "read");
   struct Release {
@@ -2223,7 +2230,7 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
   } rel{fc_, slot};
   uint8_t* b = fc_->slot_mut(slot);
   if (fused == FastClient::Ok) {
-    if (got != plen) return proxy(c, r, nullptr, 0, "short-read");
+    if (got != (ranged ? e - s + 1 : plen)) return proxy(c, r, nullptr, 0, "short-read");
     st_.sse_offloaded++;
   } else {
     if (got != size) return proxy(c, r, nullptr, 0, "short-read");
@@ -2238,8 +2245,6 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
     else if (!crypto::aes256gcm_decrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), b, b + 12, plen, b + 12 + plen))
       return proxy(c, r, nullptr, 0, "sse");
   }
-  uint64_t s = 0, e = 0;
-  int rng = parse_range(r.get("range"), plen, &s, &e);
   if (rng >= 2) return proxy(c, r, nullptr, 0, "range");
   const uint64_t from = rng == 1 ? s : 0, want = rng == 1 ? e - s + 1 : plen;
   const std::string ka = r.keep_alive ? "Connection: keep-alive\r\n" : "Connection: close\r\n";
@@ -2260,7 +2265,7 @@ bool S3Front::sse_get(Conn* c, Req& r, const std::string& meta, uint64_t size, c
     st_.sse_gets++;
     st_.bytes_out += want;
   }
-  return send_head_body(c->io(), h, b + lead + from, want);
+  return send_head_body(c->io(), h, b + lead + (ranged ? 0 : from), want);
 }
 
 // GET of a completed multipart object: the parts' sizes come from the layout the completion

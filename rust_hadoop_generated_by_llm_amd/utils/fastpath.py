@@ -121,14 +121,16 @@ class FastPathClient:
         return st, bytes.fromhex(msg) if st == OK else b""
 
     def sse_read(self, block_id: str, shm_path: str, shm_off: int, cap: int, key: bytes,
-                 request_id: str | None = None):
+                 request_id: str | None = None, offset: int = 0, length: int | None = None):
         """GET of the stored SSE-S3 blob ``block_id`` by one kernel on the chunkserver's GPU
         (csrc/fastpath.cpp op 11): the plaintext, and nothing else, lands at ``shm_off`` of the client's
         arena, which has ``cap`` bytes for it. Returns (status, n): OK, NOT_FOUND, CORRUPT, AUTH_FAILED, or UNSUPPORTED
-        when the kernel would not take it (the caller then reads and decrypts its own way)."""
-        body = struct.pack("<QQ", shm_off, cap) + _s(block_id.encode()) + _s(key) + _s(shm_path.encode())
-        body += _s(self._rid(request_id))
-        st, _total, n, _msg = self._call(11, body)
+        when the kernel would not take it (the caller then reads and decrypts its own way). With
+        ``length`` (op 12) only plaintext [offset, offset + length) is decrypted, and it lands at
+        ``shm_off + offset % 16``."""
+        head = struct.pack("<QQ", shm_off, cap) if length is None else struct.pack("<QQQQ", shm_off, cap, offset, length)
+        body = head + _s(block_id.encode()) + _s(key) + _s(shm_path.encode()) + _s(self._rid(request_id))
+        st, _total, n, _msg = self._call(11 if length is None else 12, body)
         return st, n if st == OK else 0
 
     @staticmethod

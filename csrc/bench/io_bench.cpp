@@ -1015,8 +1015,119 @@ static int sse_read_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// --sse-write: a PUT of an SSE-S3 object from a registered slot [12 free][plaintext n][16 free]. The
+// staged arm is what a PUT does without the kernel: sse_crypt in place (under its own floor), then
+// write() from the same slot; the fused arm is ChunkStore::sse_write, one sse_write_kernel launch.
+// The arms alternate inside each repetition, in both durability modes; the slot is refilled and the
+// block removed outside the timed window. One JSON line per mode and size, in the units of
+// --sse-read. `match` requires the slot after every call, and the stored bytes read back after every
+// warm-up call and the last call of every timed repetition, to equal OpenSSL's blob, and the counter
+// to prove the route.
+static int sse_write_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--sse-write needs a GPU\n");
+    return 1;
+  }
+  uint8_t key[32], nonce[12];
+  for (int i = 0; i < 32; ++i) key[i] = static_cast<uint8_t>(3 * i + 1);
+  for (int i = 0; i < 12; ++i) nonce[i] = static_cast<uint8_t>(7 * i + 5);
+  int rc = 0;
+  for (int mode = 0; mode < 2; ++mode) {
+    std::filesystem::remove_all(dir);
+    StoreConfig cfg;
+    cfg.storage_dir = dir + "/sse_write";
+    cfg.device = device;
+    cfg.hbm_capacity = 512ull << 20;
+    cfg.durability = mode == 0 ? Durability::HbmAck : Durability::NvmeSync;
+    ChunkStore s(cfg);
+    for (uint64_t n : {64ull << 10, 1ull << 20, 4ull << 20, 16ull << 20, 100ull << 20}) {
+      const auto plain = random_bytes(n, static_cast<uint32_t>(n + 37));
+      std::vector<uint8_t> blob(n + 28), back(n + 28);
+      std::memcpy(blob.data(), nonce, 12);
+      std::memcpy(blob.data() + 12, plain.data(), n);
+      crypto::aes256gcm_encrypt_inplace(key, nonce, blob.data() + 12, n, blob.data() + 12 + n);
+      uint8_t* slot = nullptr;
+      if (hipHostMalloc(reinterpret_cast<void**>(&slot), n + 64, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
+        std::fprintf(stderr, "--sse-write: no pinned slot of %llu bytes\n", static_cast<unsigned long long>(n + 64));
+        rc = 1;
+        break;
+      }
+      s.register_host(slot, n + 64);
+      const int iters = static_cast<int>(std::clamp<uint64_t>((64ull << 20) / n, 2, mode == 0 ? 100 : 20));
+      std::vector<double> us[2];  // [0] staged, [1] fused
+      bool match = true;
+      uint64_t seq = 0;
+      auto run = [&](int fused, int count, bool check_stored) {
+        set_sse_write_fused(fused != 0, 0);  // every size takes the kernel: the floor is what this measures
+        double t = 0;
+        for (int i = 0; i < count && match; ++i) {
+          const std::string id = "ssew-" + std::to_string(n) + "-" + std::to_string(seq++);
+          std::memset(slot, 0xEE, 12);
+          std::memcpy(slot + 12, plain.data(), n);
+          std::memset(slot + 12 + n, 0xEE, 16);
+          std::string err;
+          bool ok;
+          const auto t0 = Clock::now();
+          if (fused) {
+            ok = s.sse_write(id, key, nonce, slot, n).ok;
+          } else {
+            std::memcpy(slot, nonce, 12);
+            ok = s.sse_crypt(slot + 12, n, key, nonce, true, slot + 12 + n, &err) && s.write(id, slot, n + 28, 0).ok;
+          }
+          t += secs(t0, Clock::now());
+          match = ok && std::memcmp(slot, blob.data(), n + 28) == 0;
+          if (match && (check_stored || i == count - 1))  // every warm-up call, and one block of each timed repetition
+            match = s.read_into(id, 0, n + 28, back.data()).status == ReadStatus::Ok && back == blob;
+          s.remove(id);
+        }
+        return t * 1e6 / count;
+      };
+      for (int fused = 0; fused < 2; ++fused) run(fused, 2, true);  // warm-up: code objects, scratch; the stored bytes
+      const uint64_t before = s.stats().sse_fused_writes;
+      for (int rep = 0; rep < reps; ++rep)
+        for (int fused = 1; fused >= 0; --fused) us[fused].push_back(run(fused, iters, false));
+      match = match && s.stats().sse_fused_writes - before == static_cast<uint64_t>(reps) * iters;
+      auto list = [](const std::vector<double>& v) {
+        std::string o;
+        for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+        return o;
+      };
+      auto median = [](std::vector<double> v) {
+        std::sort(v.begin(), v.end());
+        return v[v.size() / 2];
+      };
+      auto spread = [](const std::vector<double>& v) { return *std::max_element(v.begin(), v.end()) - *std::min_element(v.begin(), v.end()); };
+      std::printf("{\"sse_write\": {\"durability\": \"%s\", \"bytes\": %llu, \"iters\": %d, \"fused_us\": [%s], "
+                  "\"staged_us\": [%s], \"fused_median_us\": %.1f, \"staged_median_us\": %.1f, \"fused_spread_us\": %.1f, "
+                  "\"staged_spread_us\": %.1f, \"fused_gbps\": %.2f, \"staged_gbps\": %.2f, \"match\": %s}}\n",
+                  mode == 0 ? "hbm-ack" : "nvme-sync", static_cast<unsigned long long>(n), iters, list(us[1]).c_str(),
+                  list(us[0]).c_str(), median(us[1]), median(us[0]), spread(us[1]), spread(us[0]), n / median(us[1]) / 1e3,
+                  n / median(us[0]) / 1e3, match ? "true" : "false");
+      std::fflush(stdout);
+      if (!match) rc = 1;
+      s.unregister_host(slot);
+      (void)hipHostFree(slot);
+    }
+  }
+  reset_sse_write_fused();
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 int main(int argc, char** argv) {
   dfs::trace_init();  // before any thread: roctx's first range calls setenv (trace.h)
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--sse-write") {
+      std::string dir = "/tmp/io_bench_sse_write";
+      int device = 0, reps = 5;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return sse_write_bench(device, dir, std::max(5, reps));
+    }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--sse-read") {
       std::string dir = "/tmp/io_bench_sse_read";

@@ -254,6 +254,11 @@ PYBIND11_MODULE(_dfs_native, m) {
         "GETs of stored SSE-S3 blobs verified, decrypted and delivered by one kernel (else read, then sse_crypt)",
         py::arg("on"), py::arg("min_bytes") = -1);
   m.def("sse_read_fused_min_bytes", &sse_read_fused_min_bytes, "blobs with less plaintext than this stay staged");
+  m.def("set_sse_write_fused", &set_sse_write_fused,
+        "PUTs of SSE-S3 objects encrypted, authenticated, checksummed and landed by one kernel (else sse_crypt, then write)",
+        py::arg("on"), py::arg("min_bytes") = -1);
+  m.def("reset_sse_write_fused", &reset_sse_write_fused, "route and floor back to the environment's and the defaults'");
+  m.def("sse_write_fused_min_bytes", &sse_write_fused_min_bytes, "bodies below this many bytes stay staged");
   // the shape of an sse_read_kernel launch: bytes of the blob per workgroup step, and the grid's cap
   m.attr("sse_read_tile_bytes") = kSseReadTileBytes;
   m.attr("sse_read_max_grid") = static_cast<int>(gcm::kGcmMaxGrid);
@@ -576,6 +581,31 @@ PYBIND11_MODULE(_dfs_native, m) {
       .def("sse_read_fusable", [](ChunkStore& s, const std::string& id, py::buffer out, uint64_t offset) {
         return s.sse_read_fusable(id, static_cast<const uint8_t*>(out.request().ptr), offset);
       }, py::arg("block_id"), py::arg("out_buffer"), py::arg("offset") = 0)
+      // PUT of an SSE-S3 object: the writable buffer holds the plaintext at +12 with 12 bytes free in
+      // front and 16 behind; afterwards it holds the blob [nonce][ciphertext][tag], stored as block
+      // `block_id` as write() would store it. One kernel when the buffer is registered and 16 B aligned.
+      // Returns (ok, crc of the blob, error).
+      .def("sse_write", [](ChunkStore& s, const std::string& id, py::bytes key, py::bytes nonce, py::buffer buf,
+                           bool persist_now) {
+        py::buffer_info bi = buf.request(true);
+        std::string k = key, nc = nonce;
+        const uint64_t len = static_cast<uint64_t>(bi.size * bi.itemsize);
+        if (k.size() != 32 || nc.size() != 12 || len < 29)
+          throw std::invalid_argument("sse_write: 32-byte key, 12-byte nonce, a buffer of the plaintext plus 28 bytes");
+        WriteResult w;
+        {
+          py::gil_scoped_release rel;
+          w = s.sse_write(id, reinterpret_cast<const uint8_t*>(k.data()), reinterpret_cast<const uint8_t*>(nc.data()),
+                          static_cast<uint8_t*>(bi.ptr), len - 28, persist_now);
+        }
+        gcm::wipe(&k[0], k.size());
+        return py::make_tuple(w.ok, w.actual_crc, w.error);
+      }, py::arg("block_id"), py::arg("key"), py::arg("nonce"), py::arg("buffer"), py::arg("persist_now") = true)
+      .def("sse_write_fusable", [](ChunkStore& s, py::buffer buf) {
+        py::buffer_info bi = buf.request();
+        const uint64_t len = static_cast<uint64_t>(bi.size * bi.itemsize);
+        return len >= 29 && s.sse_write_fusable(static_cast<const uint8_t*>(bi.ptr), len - 28);
+      }, py::arg("buffer"))
       // degraded read: bytes [offset, offset + length) of the RS(k, m) file whose k + m shards are
       // the resident blocks `block_ids` ("" = lost) into `out`; a registered `out` takes the
       // single-kernel path. Returns the number of bytes placed, None on failure.
@@ -955,6 +985,31 @@ PYBIND11_MODULE(_dfs_native, m) {
     gcm::wipe(&k[0], k.size());
     return ok;
   }, py::arg("key"), py::arg("nonce"), py::arg("ciphertext"), py::arg("tag"), py::arg("grid") = 0);
+  // The host half of sse_write_kernel: the tag of `ciphertext` under (key, nonce) from the partials
+  // as the kernel leaves them, the message front-aligned on whole tiles and the zero blocks behind
+  // it taken out of the fold with gcm::unfold_factor.
+  m.def("gcm_tag_unfolded", [](py::bytes key, py::bytes nonce, py::bytes ciphertext, int grid) {
+    std::string k = key, nc = nonce, c = ciphertext;
+    if (k.size() != 32 || nc.size() != 12 || c.empty())
+      throw std::invalid_argument("gcm_tag_unfolded: 32-byte key, 12-byte nonce, a ciphertext");
+    const uint64_t n = c.size();
+    const uint8_t* kp = reinterpret_cast<const uint8_t*>(k.data());
+    const gcm::Plan p = gcm::plan_for((n + 28 + (16 << 10) - 1) / (16 << 10) * (16 << 10), grid);
+    c.resize(p.nblocks * 16, '\0');
+    gcm::Keys keys;
+    std::vector<gcm::U128> part(static_cast<size_t>(p.grid));
+    uint8_t tag[16] = {0};
+    const bool ok = gcm::prepare(kp, reinterpret_cast<const uint8_t*>(nc.data()), p, &keys);
+    if (ok) {
+      gcm::ghash_partials(keys, p, reinterpret_cast<const uint8_t*>(c.data()), c.size(), part.data());
+      gcm::finish_tag(keys, gcm::unfold(gcm::ghash_fold(keys, p, part.data()), gcm::unfold_factor(keys, p.nblocks - (n + 15) / 16)),
+                      n, tag);
+    }
+    gcm::wipe(&keys, sizeof(keys));
+    gcm::wipe(&k[0], k.size());
+    if (!ok) throw std::runtime_error("gcm_tag_unfolded: AES block encryption failed");
+    return py::bytes(reinterpret_cast<const char*>(tag), 16);
+  }, py::arg("key"), py::arg("nonce"), py::arg("ciphertext"), py::arg("grid") = 0);
   m.def("rsa_sha256_verify", [](py::bytes n, py::bytes e, py::bytes msg, py::bytes sig) {
     return crypto::rsa_sha256_verify(n, e, msg, sig);
   });

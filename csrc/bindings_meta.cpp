@@ -1138,6 +1138,34 @@ void bind_meta(py::module_& m) {
         return py::make_tuple(static_cast<int>(st), py::bytes(t));
       }, py::arg("off"), py::arg("n"), py::arg("key"), py::arg("nonce"), py::arg("encrypt"), py::arg("tag") = py::bytes(),
          py::arg("request_id") = "")
+      // PUT of an SSE-S3 object sealed by the chunkserver (op 13): `plaintext` goes into a slot as
+      // [12 free][plaintext][16 free]; (status, spent, message, the slot's bytes afterwards); status 0 done,
+      // 1 not handled (slot untouched), 2 failed
+      .def("sse_write_slot", [](FastClient& c, const std::string& path, py::bytes plaintext, py::bytes key, py::bytes nonce,
+                                const std::string& etag_md5, const std::string& rid) {
+        std::string pt = plaintext, k = key, nc = nonce, msg;
+        if (k.size() != 32 || nc.size() != 12 || pt.empty())
+          throw std::invalid_argument("sse_write_slot: 32-byte key, 12-byte nonce, a plaintext");
+        const size_t n = pt.size() + 28;
+        const int64_t slot = c.acquire_slot(n);
+        if (slot < 0) throw std::runtime_error("sse_write_slot: no slot");
+        uint8_t* p = c.slot_mut(slot);
+        std::memset(p, 0, n);
+        std::memcpy(p + 12, pt.data(), pt.size());
+        FastClient::Status st;
+        FastClient::Times t;
+        int replicas = 0;
+        bool spent = false;
+        {
+          py::gil_scoped_release r;
+          st = c.sse_write_slot(path, slot, n, reinterpret_cast<const uint8_t*>(k.data()),
+                                reinterpret_cast<const uint8_t*>(nc.data()), etag_md5, &replicas, &msg, &t, rid, nullptr, &spent);
+        }
+        py::bytes after(reinterpret_cast<const char*>(p), n);
+        c.release(slot);
+        gcm::wipe(&k[0], k.size());
+        return py::make_tuple(static_cast<int>(st), spent, msg, after);
+      }, py::arg("path"), py::arg("plaintext"), py::arg("key"), py::arg("nonce"), py::arg("etag_md5"), py::arg("request_id") = "")
       .def_property_readonly("sse_gpu_ops", &FastClient::sse_gpu_ops)
       .def_property_readonly("ec_gpu_ops", &FastClient::ec_gpu_ops)
       .def_property_readonly("ec_cpu_ops", &FastClient::ec_cpu_ops)

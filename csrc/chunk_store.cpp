@@ -2565,6 +2565,7 @@ StoreStats ChunkStore::stats() {
   s.sse_fused_crypts = sse_fused_crypts_.load();
   s.sse_fused_reads = sse_fused_reads_.load();
   s.sse_fused_range_reads = sse_fused_range_reads_.load();
+  s.sse_fused_writes = sse_fused_writes_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -4336,6 +4337,132 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
   if (!whole) std::memcpy(out, pt + from, want);
   *n_out = want;
   return SseRead::Ok;
+}
+
+namespace {
+// The lane's pinned scratch of an sse_write_kernel launch: GHASH partials, CRC partials, .meta image.
+constexpr uint64_t kSseWriteCrcOff = gcm::kGcmMaxGrid * sizeof(gcm::U128);
+constexpr uint64_t kSseWriteMetaOff = kSseWriteCrcOff + gcm::kGcmMaxGrid * sizeof(uint32_t);
+}  // namespace
+
+bool ChunkStore::sse_write_fusable(const uint8_t* buf, uint64_t n) {
+  return gpu() && sse_write_fused_enabled(cfg_.durability == Durability::NvmeSync) && crc_mfma_enabled() &&
+         n >= std::max<uint64_t>(1, sse_write_fused_min_bytes()) && sse_read_tiles(n) <= (0xFFFFFFFEull >> 10) &&
+         reinterpret_cast<uintptr_t>(buf) % 16 == 0 && device_view(buf, n + 28) != nullptr;
+}
+
+WriteResult ChunkStore::sse_write(const std::string& id, const uint8_t key[32], const uint8_t nonce[12], uint8_t* buf,
+                                  uint64_t n, bool persist_now, bool fused_only, bool* declined) {
+  TraceRange tr("dfs.store.sse_write");  // no key material in ranges, logs or errors
+  if (declined) *declined = false;
+  if (!valid_block_id(id)) return bad_id(id);
+  WriteResult res;
+  if (n == 0) {
+    res.error = "an SSE body of no bytes";
+    return res;
+  }
+  const uint64_t size = n + 28;
+  uint8_t* dev = sse_write_fusable(buf, n) ? device_view(buf, size) : nullptr;
+  if (dev) {
+    HIP_OK(hipSetDevice(cfg_.device));
+    const uint64_t S = num_slices(size), s_body = sse_write_body_slices(n), ntiles = sse_read_tiles(n);
+    const gcm::Plan plan = gcm::plan_for(kSseReadTileBytes * ntiles);
+    DevExtent ext = reserve(size);
+    if (ext.off < 0) {  // the slot is untouched: the fast path's caller can still serve the write itself
+      if (declined) *declined = fused_only;
+      res.error = "HBM arena full";
+      return res;
+    }
+    auto* dmeta = reinterpret_cast<uint32_t*>(ext.ptr + align_up(size, 256));
+    Lane* l = acquire_lane();
+    ensure_hscratch(l, kSseWriteMetaOff + S * 4 + 16);
+    auto* hmeta = reinterpret_cast<uint32_t*>(l->hscratch + kSseWriteMetaOff);
+    // Nothing below throws: the lane is released and every copy of the key schedule and the powers
+    // of H that the store owns is wiped on each way out. A launch that fails has written nothing,
+    // so the call goes on to the staged route; a failure after it is an error, the slot is spent.
+    gcm::Keys keys;
+    SseWriteLaunch a{};
+    hipError_t launched = hipErrorNotReady, done = hipSuccess;
+    uint32_t block_crc = 0;
+    auto meta = std::make_shared<std::vector<uint8_t>>();
+    if (l->hscratch_dev && gcm::prepare(key, nonce, plan, &keys)) {
+      uint8_t* hdev = static_cast<uint8_t*>(l->hscratch_dev);
+      a.buf = dev;
+      a.dst = ext.ptr;
+      a.meta = dmeta;
+      a.meta_host = reinterpret_cast<uint32_t*>(hdev + kSseWriteMetaOff);
+      a.n = n;
+      a.ntiles = ntiles;
+      a.full_init = crc_init_term(kSliceBytes);
+      std::memcpy(a.nonce, keys.nonce, sizeof(a.nonce));
+      std::memcpy(a.rk, keys.rk, sizeof(a.rk));
+      a.h = keys.h;
+      a.hjump = gcm::write_jump(keys, plan);
+      std::memcpy(a.tree, keys.tree, sizeof(a.tree));
+      a.part = reinterpret_cast<gcm::U128*>(hdev);
+      a.part_crc = reinterpret_cast<uint32_t*>(hdev + kSseWriteCrcOff);
+      launched = launch_sse_write(a, dtables_, plan.grid, l->stream);
+      if (launched == hipSuccess) {
+        launches_++;
+        // H^-vback needs only the key: computed while the kernel runs
+        gcm::U128 factor = gcm::unfold_factor(keys, plan.nblocks - (n + 15) / 16);
+        done = hipStreamSynchronize(l->stream);
+        if (done == hipSuccess) {
+          // the tag, into the slot and from there into the extent
+          const gcm::U128 sum =
+              gcm::unfold(gcm::ghash_fold(keys, plan, reinterpret_cast<const gcm::U128*>(l->hscratch)), factor);
+          gcm::finish_tag(keys, sum, n, buf + 12 + n);
+          done = hipMemcpyAsync(ext.ptr + 12 + n, buf + 12 + n, 16, hipMemcpyHostToDevice, l->stream);
+          // the slices that hold tag bytes, from the slot: their .meta words and the block CRC's end
+          const uint64_t rest = size - s_body * kSliceBytes;
+          crc32_slices(buf + s_body * kSliceBytes, rest, hmeta + s_body);
+          uint32_t r = 0;
+          for (int g = 0; g < plan.grid; ++g) r ^= reinterpret_cast<const uint32_t*>(l->hscratch + kSseWriteCrcOff)[g];
+          r = crc_unshift(r, ntiles * kSseReadTileBytes - s_body * kSliceBytes);
+          r = crc_shift(r, rest) ^ crc32(buf + s_body * kSliceBytes, rest) ^ crc_init_term(rest);
+          block_crc = r ^ crc_init_term(size);
+          for (uint64_t i = s_body; i < S; ++i) hmeta[i] = __builtin_bswap32(hmeta[i]);
+          if (done == hipSuccess)
+            done = hipMemcpyAsync(dmeta + s_body, hmeta + s_body, (S - s_body) * 4, hipMemcpyHostToDevice, l->stream);
+          if (done == hipSuccess) done = hipStreamSynchronize(l->stream);
+          meta->assign(reinterpret_cast<const uint8_t*>(hmeta), reinterpret_cast<const uint8_t*>(hmeta) + S * 4);
+        }
+        gcm::wipe(&factor, sizeof(factor));
+        gcm::wipe(l->hscratch, plan.grid * sizeof(gcm::U128));
+      }
+    }
+    gcm::wipe(&a, sizeof(a));
+    gcm::wipe(&keys, sizeof(keys));
+    release_lane(l);
+    if (launched == hipSuccess) {
+      if (done != hipSuccess) {
+        release(ext);
+        res.error = std::string("SSE write kernel: ") + hipGetErrorString(done);
+        return res;
+      }
+      sse_fused_writes_++;
+      res.actual_crc = block_crc;
+      // the commit of a staged block (stage_impl without durable_now), then persist() from the slot
+      insert_resident(id, ext, size, block_crc, false, meta);
+      if (size <= kMirrorMax) set_mirror(id, buf, size, *meta);
+      if (persist_now && !persist(id, buf, size, &res.error)) {
+        remove(id);
+        return res;
+      }
+      res.ok = true;
+      return res;
+    }
+    (void)hipGetLastError();
+    release(ext);
+  }
+  if (fused_only) {
+    if (declined) *declined = true;
+    res.error = "the kernel does not take this write";
+    return res;
+  }
+  std::memcpy(buf, nonce, 12);
+  if (!sse_crypt(buf + 12, n, key, nonce, true, buf + 12 + n, &res.error)) return res;
+  return persist_now ? write(id, buf, size, 0) : stage(id, buf, size, 0);
 }
 
 bool ChunkStore::device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n) {

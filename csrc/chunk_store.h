@@ -98,6 +98,7 @@ struct StoreStats {
   uint64_t sse_fused_crypts = 0;  // SSE bodies encrypted or decrypted by one sse_gcm_kernel launch
   uint64_t sse_fused_reads = 0;   // stored SSE blobs verified, decrypted and delivered by one sse_read_kernel launch
   uint64_t sse_fused_range_reads = 0;  // of those, byte ranges by sse_read_range_kernel
+  uint64_t sse_fused_writes = 0;  // SSE PUTs encrypted, authenticated, checksummed and landed by one sse_write_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -349,6 +350,23 @@ class ChunkStore {
   SseRead sse_read(const std::string& id, const uint8_t key[32], uint8_t* out, uint64_t out_cap, uint64_t* n,
                    std::string* err, int64_t* bad_slice = nullptr, bool fused_only = false, uint64_t from = 0,
                    uint64_t want = UINT64_MAX);
+  // A PUT of an SSE-S3 object: buf[0, n + 28) holds the plaintext at buf + 12 (what stands in the
+  // other 28 bytes does not matter), n >= 1. Afterwards buf holds the blob [nonce][ciphertext][tag]
+  // and block `id` is stored exactly as write(id, buf, n + 28, 0) would have stored it: same bytes,
+  // .meta, block CRC, durability, journal or files; the result carries the blob's CRC. On a GPU store
+  // with `buf` registered and 16 B aligned, n at or above sse_write_fused_min_bytes() and the route on
+  // for the store's durability mode (sse_write_fused_enabled: hbm-ack unless switched): one extent,
+  // one sse_write_kernel launch, the host's finish (the tag, which the kernel sees as zeros, into
+  // both copies; the one or two slices that hold it checksummed from buf; the block CRC folded), then
+  // the commit of a staged block and persist() from buf. The durable copy starts only after the
+  // kernel, where write() overlaps its data file with the GPU. Otherwise the staged route: the nonce
+  // copied in, sse_crypt in place, write(). With persist_now false the block is staged only, as
+  // stage() leaves it, and persist(id, buf, n + 28) completes it. With fused_only the call declines
+  // (ok false, *declined set, buf untouched) instead of taking the staged route. Nothing outside
+  // [buf, buf + n + 28) is written. The key schedule and the powers of H are wiped before this returns.
+  bool sse_write_fusable(const uint8_t* buf, uint64_t n);  // would sse_write take the kernel
+  WriteResult sse_write(const std::string& id, const uint8_t key[32], const uint8_t nonce[12], uint8_t* buf, uint64_t n,
+                        bool persist_now = true, bool fused_only = false, bool* declined = nullptr);
   // Device bytes into host memory (registered: one DMA) and synchronously complete.
   bool device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n);
   // A copy of device bytes committed as block `id` (checksummed, verified, made durable).
@@ -553,7 +571,7 @@ class ChunkStore {
                 std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
   const uint8_t* sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size, uint64_t from, uint64_t want);
   std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0},
-      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0};
+      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0}, sse_fused_writes_{0};
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

@@ -298,15 +298,17 @@ bool FastClient::call(const std::string& sock, const std::string& method_path, c
 }
 
 bool FastClient::fp_call(uint8_t op, const std::string& body, uint8_t* status, uint64_t* total, uint64_t* nbytes,
-                         std::string* msg) {
-  return fp_call_to(fp_socket_, op, body, status, total, nbytes, msg);
+                         std::string* msg, bool* reached) {
+  return fp_call_to(fp_socket_, op, body, status, total, nbytes, msg, reached);
 }
 
 bool FastClient::fp_call_to(const std::string& sock, uint8_t op, const std::string& body, uint8_t* status,
-                            uint64_t* total, uint64_t* nbytes, std::string* msg) {
+                            uint64_t* total, uint64_t* nbytes, std::string* msg, bool* reached) {
   const std::string& fp_socket_ = sock;  // the connection pool is keyed by socket name
+  if (reached) *reached = false;
   int fd = take_conn(fp_socket_);
   if (fd < 0) return false;
+  if (reached) *reached = true;  // from here on the server may have the request, whatever comes back
   std::string req;
   put<uint32_t>(req, static_cast<uint32_t>(body.size() + 1));
   req.push_back(static_cast<char>(op));
@@ -389,10 +391,24 @@ FastClient::Status FastClient::write_slot(const std::string& path, int64_t slot,
   return write_slot_impl(path, slot, n, replicas, msg, t, rid_in, attrs, etag_attr, md5_out, nullptr);
 }
 
+FastClient::Status FastClient::sse_write_slot(const std::string& path, int64_t slot, size_t n, const uint8_t key[32],
+                                              const uint8_t nonce[12], const std::string& etag_md5, int* replicas,
+                                              std::string* msg, Times* t, const std::string& rid_in,
+                                              const std::map<std::string, std::string>* attrs, bool* spent) {
+  bool own = false;
+  if (!spent) spent = &own;
+  *spent = false;
+  if (n < 29) return NotHandled;
+  const SseSeal seal{key, nonce, &etag_md5, spent};
+  std::string md5;
+  return write_slot_impl(path, slot, n, replicas, msg, t, rid_in, attrs, nullptr, &md5, nullptr, &seal);
+}
+
 FastClient::Status FastClient::write_slot_impl(const std::string& path, int64_t slot, size_t n, int* replicas,
                                                std::string* msg, Times* t, const std::string& rid_in,
                                                const std::map<std::string, std::string>* attrs,
-                                               const char* etag_attr, std::string* md5_out, Hashes* pre) {
+                                               const char* etag_attr, std::string* md5_out, Hashes* pre,
+                                               const SseSeal* sse) {
   const std::string rid = rid_in.empty() ? new_request_id() : rid_in;
   RequestScope rs(rid);
   TraceRange tr("dfs.client.write");
@@ -410,11 +426,12 @@ FastClient::Status FastClient::write_slot_impl(const std::string& path, int64_t 
     ~Join() { h.wait(); }
   } join{own};
   Hashes& h = pre ? *pre : own;
-  if (!pre) start_hashes(data, n, false, &own);
+  // sealed by the chunkserver (op 13): the slot holds plaintext, the ETag is given and the CRC comes back
+  if (!pre && !sse) start_hashes(data, n, false, &own);
   std::future<std::string>& md5 = h.md5;
   uint32_t crc = 0;
-  bool have_crc = false;
-  if (!h.crc.valid()) {
+  bool have_crc = sse != nullptr;
+  if (!sse && !h.crc.valid()) {
     crc = crc32(data, n);
     have_crc = true;
   }
@@ -453,11 +470,17 @@ FastClient::Status FastClient::write_slot_impl(const std::string& path, int64_t 
 
   std::string body;
   put<uint64_t>(body, alloc.master_term);
-  put<uint32_t>(body, crc);
+  if (!sse) put<uint32_t>(body, crc);
   put<uint64_t>(body, static_cast<uint64_t>(slot));
   put<uint64_t>(body, n);
   put_str(body, alloc.block.block_id);
   put_str(body, arena_path_);
+  if (sse) {
+    put<uint16_t>(body, 32);  // straight into `body`, which is wiped: no temporary holds the key
+    body.append(reinterpret_cast<const char*>(sse->key), 32);
+    put<uint16_t>(body, 12);
+    body.append(reinterpret_cast<const char*>(sse->nonce), 12);
+  }
   put<uint16_t>(body, static_cast<uint16_t>(alloc.chunk_server_addresses.size() - 1));
   for (size_t i = 1; i < alloc.chunk_server_addresses.size(); ++i)
     put_str(body, strip_scheme(alloc.chunk_server_addresses[i]));
@@ -465,20 +488,40 @@ FastClient::Status FastClient::write_slot_impl(const std::string& path, int64_t 
   uint8_t st;
   uint64_t total, written;
   std::string fmsg;
-  bool sent = fp_call(1, body, &st, &total, &written, &fmsg);
+  bool reached = false;
+  bool sent = fp_call(sse ? 13 : 1, body, &st, &total, &written, &fmsg, &reached);
+  if (sse) gcm::wipe(&body[0], body.size());
+  // An op 13 lost on a connection that stood may have reached the server, which may run the kernel over
+  // the slot now or later: the slot counts as spent. Only a connection that never stood is NotHandled.
+  if (!sent && sse && reached) {
+    *sse->spent = true;
+    *msg = "Failed to write block: fast path connection lost";
+    return Failed;
+  }
   if (!sent) return NotHandled;
   if (st == 5 || st == 4) {  // fenced / I/O error: what the gRPC path would report
+    if (sse) *sse->spent = st == 4;  // op 13 fences before it touches the slot
     *msg = "Failed to write block: " + fmsg;
     return Failed;
   }
-  if (st != 0) return NotHandled;
+  if (st != 0) return NotHandled;  // op 13 answers these only while the slot is untouched
+  if (sse) {
+    *sse->spent = true;
+    char* end = nullptr;
+    crc = static_cast<uint32_t>(std::strtoul(fmsg.c_str(), &end, 16));
+    if (fmsg.size() != 8 || *end) {
+      *msg = "Failed to write block: malformed checksum in the reply";
+      return Failed;
+    }
+    sse_gpu_++;
+  }
   *replicas = static_cast<int>(written);
   t->write = since(clk);
 
   pb::CompleteFileRequest done;
   done.path = path;
   done.size = n;
-  done.etag_md5 = md5.get();
+  done.etag_md5 = sse ? *sse->md5 : md5.get();
   *md5_out = done.etag_md5;
   t->md5_wait = since(clk);
   done.created_at_ms = static_cast<uint64_t>(now_ms());

@@ -101,6 +101,18 @@ class FastClient {
   Status write_slot(const std::string& path, int64_t slot, size_t n, int* replicas, std::string* msg, Times* t,
                     const std::string& rid, const std::map<std::string, std::string>* attrs, const char* etag_attr,
                     std::string* md5_out);
+  // write_slot() of an SSE-S3 PUT sealed where it is stored: `slot` holds [12 free][plaintext][16 free],
+  // n bytes in all (the blob's size). CreateFile, fast-path op 13 (the co-located chunkserver encrypts,
+  // authenticates, checksums and stores the blob in one kernel, and leaves it in the slot), CompleteFile
+  // with the CRC from the reply and `etag_md5`, the plaintext's MD5 that the caller computed: the
+  // ciphertext is never hashed here. NotHandled: the slot is untouched and the caller goes on its own
+  // way. Failed with *spent set came after the op was sent (IoError, a lost connection, a malformed
+  // reply, CompleteFile, whose "already exists" means a concurrent PUT of the key won): the slot may
+  // hold the blob, so the call must not be repeated over it. Failed without it came from CreateFile
+  // or a fence, with the slot as the caller left it.
+  Status sse_write_slot(const std::string& path, int64_t slot, size_t n, const uint8_t key[32], const uint8_t nonce[12],
+                        const std::string& etag_md5, int* replicas, std::string* msg, Times* t, const std::string& rid,
+                        const std::map<std::string, std::string>* attrs, bool* spent = nullptr);
   // The distinct next path components below `prefix` on every shard (ListFiles with the
   // delimiter extension: one entry per component from each master, not every path).
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid);
@@ -161,10 +173,11 @@ class FastClient {
   bool call(const std::string& sock, const std::string& method_path, const std::string& rid, const std::string& req,
             int* code,
             std::string* resp);
+  // *reached (optional): a connection stood and the request may have been received, answered or not
   bool fp_call(uint8_t op, const std::string& body, uint8_t* status, uint64_t* total, uint64_t* nbytes,
-               std::string* msg);
+               std::string* msg, bool* reached = nullptr);
   bool fp_call_to(const std::string& sock, uint8_t op, const std::string& body, uint8_t* status, uint64_t* total,
-                  uint64_t* nbytes, std::string* msg);
+                  uint64_t* nbytes, std::string* msg, bool* reached = nullptr);
   std::string peer_fastpath(const std::string& addr) const;  // "" unless `addr` is on this host
   bool ec_matmul(const std::vector<std::vector<uint8_t>>& mat, int k, uint64_t len, uint64_t in_off, uint64_t out_off,
                  const std::vector<uint16_t>* idx, const std::string& rid);
@@ -202,9 +215,15 @@ class FastClient {
     }
   };
   void start_hashes(const uint8_t* p, size_t n, bool with_crc, Hashes* h);
+  struct SseSeal {  // an op 13 write: the object's data key, its nonce, the plaintext's MD5
+    const uint8_t* key;
+    const uint8_t* nonce;
+    const std::string* md5;
+    bool* spent;
+  };
   Status write_slot_impl(const std::string& path, int64_t slot, size_t n, int* replicas, std::string* msg, Times* t,
                          const std::string& rid, const std::map<std::string, std::string>* attrs,
-                         const char* etag_attr, std::string* md5_out, Hashes* pre);
+                         const char* etag_attr, std::string* md5_out, Hashes* pre, const SseSeal* sse = nullptr);
   // MD5 workers (the etag is a strictly sequential hash: overlap it with the RPCs)
   std::mutex q_mu_;
   std::condition_variable q_cv_;

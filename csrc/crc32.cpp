@@ -189,6 +189,11 @@ uint32_t crc_shift(uint32_t v, uint64_t nbytes) {
   return v;
 }
 
+uint32_t crc_unshift(uint32_t v, uint64_t nbytes) {
+  constexpr uint64_t kOrder = 0xFFFFFFFFull;  // x^(2^32 - 1) = 1 modulo the (irreducible) polynomial
+  return crc_shift(v, kOrder - nbytes % kOrder);
+}
+
 Gf2Mat shift_matrix(uint64_t nbytes) {
   Gf2Mat r;
   for (int i = 0; i < 32; ++i) r.col[i] = 1u << i;

@@ -41,6 +41,9 @@ Gf2Mat gf2_mul(const Gf2Mat& a, const Gf2Mat& b);  // a∘b
 const Gf2Mat& shift_pow2_bytes(int b);
 // Raw-register shift by n zero bytes.
 uint32_t crc_shift(uint32_t v, uint64_t nbytes);
+// The inverse: the register that n zero bytes turned into v (a shift by 2^32 - 1 - n bytes: the
+// shift by one byte is multiplication by x^8, whose order divides 2^32 - 1).
+uint32_t crc_unshift(uint32_t v, uint64_t nbytes);
 Gf2Mat shift_matrix(uint64_t nbytes);
 // S(n) = shift(0xFFFFFFFF, n) ^ 0xFFFFFFFF : crc32(d) = R(d) ^ S(|d|).
 uint32_t crc_init_term(uint64_t nbytes);

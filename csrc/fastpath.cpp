@@ -14,6 +14,7 @@
 
 #include <cerrno>
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <future>
 
@@ -747,7 +748,8 @@ void FastPathServer::serve(int fd) {
   };
   // Local persist and the downstream fan-out run concurrently; the ack waits for both.
   auto persist_and_forward = [&](const std::string& id, const uint8_t* host, uint64_t len, uint32_t crc,
-                                 uint64_t term, const std::vector<std::string>& next, const ShmSrc& src) -> bool {
+                                 uint64_t term, const std::vector<std::string>& next, const ShmSrc& src,
+                                 const std::string& ok_msg = std::string()) -> bool {
     int down = 0;
     std::string perr;
     const std::string rid = t_request_id;
@@ -758,7 +760,7 @@ void FastPathServer::serve(int fd) {
     bool pok = store_->persist(id, host, host ? len : 0, &perr);
     fut.get();
     if (!pok) return send_response(fd, FpStatus::IoError, 0, 0, perr);
-    return send_response(fd, FpStatus::Ok, len, 1 + static_cast<uint64_t>(down), "");
+    return send_response(fd, FpStatus::Ok, len, 1 + static_cast<uint64_t>(down), ok_msg);
   };
   while (!stop_.load()) {
     uint32_t n = 0;
@@ -1011,6 +1013,50 @@ void FastPathServer::serve(int fd) {
             sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU, slot not pinned, block not resident or below the kernel's floor");
             break;
           default: sent = send_response(fd, FpStatus::IoError, 0, 0, err); break;
+        }
+      }
+      gcm::wipe(&key[0], key.size());
+      gcm::wipe(body.data(), body.size());
+    } else if (op == 13) {  // SSE_WRITE: the plaintext in the client's slot encrypted, checksummed and landed by one kernel
+      const uint64_t term = rd.get<uint64_t>();
+      const uint64_t off = rd.get<uint64_t>(), len = rd.get<uint64_t>();
+      std::string id = rd.str(), path = rd.str(), key = rd.str(), nonce = rd.str();
+      std::vector<std::string> next = read_list(rd, true);
+      std::string rid = rd.p < rd.end ? rd.str() : std::string();
+      RequestScope rs(rid);
+      note_rid(rid);
+      TraceRange tr("dfs.fp.sse_write");  // the key stays out of ranges, logs and answers
+      std::string err;
+      uint8_t* base = nullptr;
+      if (!rd.ok || id.empty() || key.size() != 32 || nonce.size() != 12 || len < 29 || len > kMaxTransfer ||
+          off > (1ull << 62)) {
+        sent = send_response(fd, FpStatus::BadRequest, 0, 0, "malformed sse write request");
+      } else if (fenced(term, &msg)) {
+        sent = send_response(fd, FpStatus::Fenced, term_.load(), 0, msg);
+      } else if (!all_local(next)) {
+        sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no native route for a replica");
+      } else if ((base = map_shm(path, off, len, &err)) == nullptr) {
+        sent = send_response(fd, FpStatus::Unsupported, 0, 0, "short-circuit unavailable: " + err);
+      } else {
+        if (store_->gpu()) {  // a new arena is pinned off this thread: the first body waits for that instead of losing the GPU
+          std::unique_lock<std::mutex> lk(mu_);
+          workers_cv_.wait(lk, [this] { return pending_regs_ == 0; });
+        }
+        // the kernel or nothing: declined means the slot is as the client left it
+        bool declined = false;
+        WriteResult wr = store_->sse_write(id, reinterpret_cast<const uint8_t*>(key.data()),
+                                           reinterpret_cast<const uint8_t*>(nonce.data()), base + off, len - 28, false, true,
+                                           &declined);
+        if (declined) {
+          sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU, slot not pinned or body below the kernel's floor");
+        } else if (!wr.ok) {
+          sent = send_response(fd, FpStatus::IoError, 0, 0, wr.error);
+        } else {
+          bump(&FpStats::sse_writes);
+          char hex[9];
+          std::snprintf(hex, sizeof(hex), "%08x", wr.actual_crc);
+          // the slot holds the blob now: durable here and out to the replicas as any staged write
+          sent = persist_and_forward(id, base + off, len, wr.actual_crc, term, next, ShmSrc{path, off, len}, hex);
         }
       }
       gcm::wipe(&key[0], key.size());

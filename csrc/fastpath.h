@@ -52,6 +52,14 @@
 //               authenticated, plaintext [from, from + want) alone decrypted and stored at shm_off + from % 16
 //               of the client's slot (cap counts from shm_off); answers as op 11 with bytes = want and
 //               total = the blob's size. want == 0 is BadRequest; a range past the plaintext's end IoError.
+//     op 13 SSE_WRITE: u64 term | u64 shm_off | u64 len | u16 id | u16 path | u16 key(32) | u16 nonce(12)
+//               [| u16 n_next | (u16 len addr)*] [| u16 rid]  -- PUT of an SSE-S3 object by sse_write_kernel: the
+//               slot holds [12 free][plaintext len - 28][16 free] at shm_off and afterwards the blob
+//               [nonce][ciphertext][tag], stored as block `id`, persisted and fanned out to `next` as op 1
+//               does; answers Ok with bytes = replicas written and msg = the blob's CRC-32 as 8 hex digits.
+//               Unsupported only while the slot is untouched (ChunkStore::sse_write_fusable says no, a
+//               replica off this host, the arena not mapped or pinned): the client then encrypts and writes
+//               its own way. Fenced, BadRequest (key or nonce length, len < 29), IoError after the launch.
 //   response = u32 body_len | u8 status | u64 total | u64 bytes | u16 msg_len msg
 //   (for WRITE/REPL ``bytes`` carries replicas_written; for CTRL ``msg`` is the engine reply)
 //
@@ -101,6 +109,7 @@ struct FpStats {
   uint64_t ec_ops = 0;            // erasure-coding matrix products run for clients
   uint64_t sse_crypts = 0;        // SSE bodies encrypted or decrypted in clients' slots
   uint64_t sse_reads = 0;         // stored SSE blobs decrypted into clients' slots by one kernel
+  uint64_t sse_writes = 0;        // SSE bodies encrypted in clients' slots and stored by one kernel
   uint64_t heals_out = 0, heals_in = 0;  // heal / balancer copies sent / received on the engine
   uint64_t sliced_writes = 0;  // head writes whose replica sends overlapped the staging
   // device-resident erasure coding: EC writes whose shards were encoded and scattered HBM ->

@@ -83,6 +83,18 @@ class FrontStore {
     (void)meta_pb, (void)key, (void)slot, (void)n, (void)rid, (void)from, (void)want, (void)lead;
     return FastClient::NotHandled;
   }
+  // PUT of an SSE-S3 object sealed where it is stored (FastClient::sse_write_slot): `slot` holds
+  // [12 free][plaintext][16 free], n bytes in all. NotHandled, the default and whenever the slot is
+  // untouched: the caller encrypts and writes itself. Failed sets *spent when it came after the op.
+  virtual Status sse_write_slot(const std::string& path, int64_t slot, size_t n, const uint8_t key[32],
+                                const uint8_t nonce[12], const std::string& etag_md5, int* replicas, std::string* msg,
+                                Times* t, const std::string& rid, const std::map<std::string, std::string>* attrs,
+                                bool* spent = nullptr) {
+    (void)path, (void)slot, (void)n, (void)key, (void)nonce, (void)etag_md5, (void)replicas, (void)msg, (void)t, (void)rid,
+        (void)attrs;
+    if (spent) *spent = false;
+    return FastClient::NotHandled;
+  }
   // calls a first-choice path declined and a second one served (LocalFirstFrontStore)
   virtual uint64_t fallbacks() const { return 0; }
 };
@@ -129,6 +141,11 @@ class FastFrontStore final : public FrontStore {
   Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
                   uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr) override {
     return fc_->sse_read(meta_pb, key, slot, n, rid, from, want, lead);
+  }
+  Status sse_write_slot(const std::string& path, int64_t slot, size_t n, const uint8_t key[32], const uint8_t nonce[12],
+                        const std::string& etag_md5, int* replicas, std::string* msg, Times* t, const std::string& rid,
+                        const std::map<std::string, std::string>* attrs, bool* spent = nullptr) override {
+    return fc_->sse_write_slot(path, slot, n, key, nonce, etag_md5, replicas, msg, t, rid, attrs, spent);
   }
 
  private:
@@ -210,6 +227,11 @@ class LocalFirstFrontStore final : public FrontStore {
   Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
                   uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr) override {
     return fc_->sse_read(meta_pb, key, slot, n, rid, from, want, lead);
+  }
+  Status sse_write_slot(const std::string& path, int64_t slot, size_t n, const uint8_t key[32], const uint8_t nonce[12],
+                        const std::string& etag_md5, int* replicas, std::string* msg, Times* t, const std::string& rid,
+                        const std::map<std::string, std::string>* attrs, bool* spent = nullptr) override {
+    return fc_->sse_write_slot(path, slot, n, key, nonce, etag_md5, replicas, msg, t, rid, attrs, spent);
   }
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid) override {
     if (fc_->list_components(prefix, out, rid) == FastClient::Ok) return FastClient::Ok;

@@ -167,6 +167,22 @@ bool tag_matches(const Keys& k, U128 folded, uint64_t n, uint64_t vback, const u
   return ok;
 }
 
+U128 unfold_factor(const Keys& k, uint64_t vback) {
+  if (vback == 0) return kOne;
+  // the exponent 2^128 - 1 - vback is the complement of vback: its high 64 bits are all ones
+  U128 r = kOne, h = k.h;
+  for (int i = 0; i < 128; ++i) {
+    if (i >= 64 || ((~vback >> i) & 1)) r = gf128_mul(h, r);
+    h = gf128_mul(h, h);
+  }
+  wipe(&h, sizeof(h));
+  return r;
+}
+
+U128 write_jump(const Keys& k, const Plan& p) {
+  return gf128_pow(k.h, static_cast<uint64_t>(kGcmTileBlocks) * std::max(p.grid, 1) - (kGcmLaneBlocks + 1));
+}
+
 void ghash_partials(const Keys& k, const Plan& p, const uint8_t* data, uint64_t n, U128* part) {
   constexpr int kLanes = kGcmTileBlocks / kGcmLaneBlocks;
   std::vector<U128> acc(kLanes);

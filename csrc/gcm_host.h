@@ -142,6 +142,15 @@ bool set_nonce(const uint8_t key[32], const uint8_t nonce[12], Keys* k);
 // change GHASH and H has no cheap inverse, so the comparison is made one multiply further on, where
 // both sides can be computed: folded * H == ((tag ^ E_K(J0)) ^ len * H) * H^vback. Constant time.
 bool tag_matches(const Keys& k, U128 folded, uint64_t n, uint64_t vback, const uint8_t tag[16]);
+// For a kernel that folds with `vback` zero blocks behind the message and must produce the tag
+// (sse_write_kernel): unfold_factor is H^-vback, by Fermat H^(2^128 - 1 - vback), one square-and-
+// multiply over a 128-bit exponent (some 250 multiplies, ~150 us measured, needing only the key: the caller
+// computes it while the kernel runs), and unfold(folded, factor) the message's own sum, which
+// finish_tag closes. vback == 0 costs nothing.
+U128 unfold_factor(const Keys& k, uint64_t vback);
+inline U128 unfold(U128 folded, U128 factor) { return gf128_mul(factor, folded); }
+// sse_write_kernel's step between a lane's tiles: its chunk absorbs five elements, not four.
+U128 write_jump(const Keys& k, const Plan& p);
 // The workgroup partials as the kernel leaves them, computed on the host: [p.grid].
 void ghash_partials(const Keys& k, const Plan& p, const uint8_t* data, uint64_t n, U128* part);
 // Fold per-workgroup partials into sum C_i * H^(nblocks - i), close with the length block

@@ -23,6 +23,9 @@
 //   K7 range read  sse_read_range_kernel: a Range GET of an SSE-S3 object — every tile of the blob
 //          verified and authenticated as above, the CTR keystream computed and the plaintext stored
 //          only for the tiles that hold bytes of the range.
+//   K7 write  sse_write_kernel: a PUT of an SSE-S3 object in one pass over the gateway's slot — the
+//          plaintext loaded over PCIe, encrypted and authenticated in registers, the slices
+//          checksummed on the matrix cores, and the blob stored to its HBM extent and back in place.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -334,6 +337,49 @@ struct SseReadRangeLaunch {
   uint64_t from, want;
 };
 hipError_t launch_sse_read_range(const SseReadRangeLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// K7 write (sse_write_kernel): an SSE-S3 PUT in one pass. `buf` is the 16 B aligned device view of
+// registered host memory of n + 28 bytes holding [12 unspecified][plaintext n][16 unspecified], n >= 1;
+// `dst` a 16 B aligned HBM extent padded to 16 B and `meta` its .meta image. The kernel encrypts
+// with the counter built from `nonce` (the argument, not the slot's bytes), stores
+// [nonce][ciphertext][zeros] to dst and back to buf, writing nothing outside [buf, buf + n + 28), and
+// leaves: the BE .meta words of the sse_write_body_slices(n) slices in front of the tag in `meta`
+// and `meta_host`; in `part` the GHASH partials of the plan gcm::plan_for(kSseReadTileBytes * ntiles),
+// ntiles = sse_read_tiles(n), whose grid is the launch's; and in `part_crc` the raw whole-block CRC
+// partials of those slices followed by zeros to the end of the last tile (XOR them, then take the
+// zeros out with crc_unshift). The key schedule and the powers of H are gcm::prepare's for that
+// plan, except `hjump`: a chunk absorbs five elements, so a lane's step between its tiles is
+// gcm::write_jump. The host closes the tag (gcm::unfold takes out the plan's zero blocks behind
+// the message), writes it to both copies and checksums the slices that hold it. meta_host, part and
+// part_crc are device-visible host words.
+constexpr uint64_t sse_write_body_slices(uint64_t n) { return (n + 12) / 512; }
+struct SseWriteLaunch {
+  uint8_t* buf;
+  uint8_t* dst;
+  uint32_t* meta;
+  uint32_t* meta_host;
+  uint64_t n, ntiles;
+  uint32_t full_init;  // S(512)
+  uint32_t nonce[3];
+  uint32_t rk[60];
+  gcm::U128 h, hjump, tree[gcm::kGcmTreeSteps];
+  gcm::U128* part;     // [grid]
+  uint32_t* part_crc;  // [grid]
+};
+// The staged route is sse_crypt in place, then write. Measured (profiles/r13), the kernel wins from
+// 4 MiB up on an hbm-ack store (320 against 381 us) and at no size on an nvme-sync store, where the
+// durable copy can start only after the kernel while write() overlaps its data file with the GPU.
+// So with nothing said the kernel takes bodies of sse_write_fused_min_bytes() and more on hbm-ack
+// stores only; DFS_SSE_WRITE_FUSED=1 or set_sse_write_fused(true) turns it on in both modes, =0 or
+// (false) off. DFS_SSE_WRITE_FUSED_MIN_BYTES overrides the floor; the setter is the benches' and
+// tests' switch (min_bytes < 0 keeps the floor), and reset_sse_write_fused puts both back to what
+// the environment and the defaults say, the "nothing said" state included.
+constexpr uint64_t kSseWriteFusedMinBytes = 4ull << 20;
+bool sse_write_fused_enabled(bool nvme_sync);
+uint64_t sse_write_fused_min_bytes();
+void set_sse_write_fused(bool on, int64_t min_bytes = -1);
+void reset_sse_write_fused();
+hipError_t launch_sse_write(const SseWriteLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

@@ -2376,6 +2376,177 @@ __global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2
   if (threadIdx.x == 0) a.part_bad[blockIdx.x] = wg_bad;
 }
 
+// ---- K7 write: encrypt, authenticate, checksum and land an SSE-S3 PUT in one pass ----
+//
+// The mirror of sse_read_kernel, on the same axis: the slot holds [nonce 12][plaintext n][16 free],
+// tile T is blob bytes [16 KiB * T, 16 KiB * (T + 1)), thread t owns the 64 B chunk at vectors
+// g = 1024 T + 4t .. g + 3. Both the slot and the extent are 16 B aligned, so vector v is loaded
+// from buf + 16v and its ciphertext stored to dst + 16v and back to buf + 16v, unshifted.
+//
+// Nothing crosses a lane. A chunk touches five AES blocks: dwords 1..3 of block g - 1 (the chunk's
+// first three dwords), blocks g .. g + 2 whole, and dword 0 of block g + 3 (its last). The lane
+// computes all five counters' keystream (the fifth block rides in the rounds of the other four) and
+// so holds its whole ciphertext chunk: the CRC's operand, and what it stores. Because a lane reads
+// and writes its own four vectors only, encrypting in place has no ordering to respect.
+//   GHASH is linear in the block, so the two split blocks are absorbed as two elements each, one by
+// either owner, zero where the other's dwords stand: five absorbs per chunk (tail of block g - 1,
+// three whole blocks, head of block g + 3), and the step between a lane's tiles is
+// H^(1024 * grid - 5). The lane again stands at the end of block g + 3, so the tree, the partials
+// and gcm::ghash_fold are those of sse_read_kernel. The nonce (vector 0, dwords 0..2) is stored from
+// the arguments and is no part of any element; every byte from 12 + n on counts as zero whatever the slot
+// holds there, so the tag's room and the padding are stored as zeros and the host, which alone can
+// close the tag, writes it afterwards.
+//
+// CRC. The ciphertext chunk goes through the permlane32 route of sse_read_kernel into the MFMA
+// operand. Slices that lie wholly in front of the tag (s < (n + 12) / 512) get their .meta word
+// here, in HBM and in the host image; the one or two behind them hold tag bytes and are the host's.
+// The same slices feed the whole-block CRC: sub-tile CRCs, a Horner step of `grid` tiles between a
+// workgroup's tiles, and the partial moved to the end of the tile axis as crc_write_copy_kernel
+// does. The zeros behind the last such slice are part of that value; the host takes them out again
+// (the shift by zero bytes is invertible: x has an inverse modulo the CRC polynomial).
+//
+// Registers as sse_read_kernel: two waves per SIMD, no scratch.
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void sse_write_kernel(
+    SseWriteLaunch a, const DevCrcTables* __restrict__ gt) {
+  static_assert(kCrcWgThreads == 256 && gcm::kGcmTileBlocks * 16 == kSlicesPerTile * 512, "a CRC tile is a GCM tile");
+  __shared__ MfmaTileLds lt;
+  __shared__ uint32_t te0[256];
+  __shared__ uint8_t sbox[256];
+  __shared__ gcm::U128 wave_part[4];
+  __shared__ uint32_t wacc[4];
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int64_t n = static_cast<int64_t>(a.n), size = n + 28, nvec = (size + 15) / 16;
+  const int64_t s_body = static_cast<int64_t>(sse_write_body_slices(a.n));
+  const u32x4* src = reinterpret_cast<const u32x4*>(a.buf);  // aliases the stores back: no __restrict__
+  auto first_vector = [&](uint64_t tile) { return static_cast<int64_t>(tile * gcm::kGcmTileBlocks + 4 * threadIdx.x); };
+  auto fetch = [&](uint64_t tile, uint4 (&v)[4]) {
+    const int64_t g = first_vector(tile);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[i] = make_uint4(0, 0, 0, 0);
+      if (g + i < nvec) {  // the vector behind the slot's end is never loaded
+        const u32x4 x = __builtin_nontemporal_load(src + g + i);
+        v[i] = make_uint4(x[0], x[1], x[2], x[3]);
+      }
+    }
+  };
+
+  uint4 cur[4];
+  fetch(blockIdx.x, cur);  // the link's latency first
+  i32x4 A[16];
+  load_basis(reinterpret_cast<const i32x4*>(gt + 1), lane, A);
+  load_lds_image(gt, &lt);
+  sse_load_tables(gt, te0, sbox);
+  __syncthreads();
+
+  gcm::U128 acc{0, 0};
+  uint32_t crc = 0;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    uint4 nxt[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+    if (tile + gridDim.x < a.ntiles) fetch(tile + gridDim.x, nxt);
+    const int64_t g = first_vector(tile);
+    const uint32_t d[16] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                            cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+
+    // the keystream of blocks g - 1 .. g + 3; chunk dword i takes dword (i + 1) % 4 of block g - 1 + (i + 1) / 4
+    uint32_t ks[5][4];
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      ks[b][0] = a.nonce[0];
+      ks[b][1] = a.nonce[1];
+      ks[b][2] = a.nonce[2];
+      ks[b][3] = gcm::bswap32(1u + static_cast<uint32_t>(g + b));
+    }
+    gcm::aes256_encrypt_words<5>(te0, sbox, a.rk, ks);
+    uint32_t c[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int64_t p = 16 * g + 4 * i;  // the dword's first byte in the blob
+      c[i] = p < 12 ? a.nonce[i & 3] : (d[i] ^ ks[(i + 1) >> 2][(i + 1) & 3]) & sse_keep(12 + n - p);
+    }
+
+    // land: the extent is padded to 16 B, the slot ends where the blob does
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t pos = 16 * (g + i);
+      if (pos >= size) continue;
+      const uint4 v = make_uint4(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+      *reinterpret_cast<uint4*>(a.dst + pos) = v;
+      if (pos + 16 <= size) {
+        *reinterpret_cast<uint4*>(a.buf + pos) = v;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (pos + j < size) a.buf[pos + j] = static_cast<uint8_t>(c[4 * i + (j >> 2)] >> (8 * (j & 3)));
+      }
+    }
+
+    // checksum: the chunk, halves exchanged across the half-waves into the MFMA's operand
+    {
+      uint32_t p0[8], p1[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const auto r = __builtin_amdgcn_permlane32_swap(c[k], c[8 + k], false, false);
+        p0[k] = r[0];
+        p1[k] = r[1];
+      }
+      WaveData w;
+      w.v[0] = make_uint4(p0[0], p0[1], p0[2], p0[3]);
+      w.v[1] = make_uint4(p0[4], p0[5], p0[6], p0[7]);
+      w.v[2] = make_uint4(p1[0], p1[1], p1[2], p1[3]);
+      w.v[3] = make_uint4(p1[4], p1[5], p1[6], p1[7]);
+      uint32_t r = slice_from_chunks(lt, wave_chunk_crcs(A, w, lane), lane);
+      const int64_t i = static_cast<int64_t>(tile) * kSlicesPerTile + wave * 8 + sw;
+      if (i >= s_body) {
+        r = 0;  // the host's slices, and zeros to the whole-block CRC
+      } else if (sl == 0) {
+        const uint32_t be = __builtin_bswap32(r ^ a.full_init);
+        a.meta[i] = be;
+        a.meta_host[i] = be;
+      }
+      r = combine<8>(r, lane, lt.sh512);
+      r = combine<16>(r, lane, lt.sh1k);
+      r = combine<32>(r, lane, lt.sh2k);  // wave-uniform: the 4 KiB sub-tile's raw CRC
+      if (tile != blockIdx.x) {
+        uint32_t e = gridDim.x;
+        for (int b = 0; e; ++b, e >>= 1)
+          if (e & 1) crc = mat_apply(lt.tile_pow2[b], crc, lane);
+      }
+      crc ^= r;
+    }
+
+    // authenticate: the tail of block g - 1, blocks g .. g + 2, the head of block g + 3
+    if (tile != blockIdx.x) acc = gcm::gf128_mul(a.hjump, acc);
+    {
+      const bool head = g == 0;  // the nonce stands where block -1's tail would
+      const uint32_t e0[4] = {0, head ? 0 : c[0], head ? 0 : c[1], head ? 0 : c[2]};
+      acc = ghash_absorb(acc, a.h, e0);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const uint32_t e[4] = {c[4 * b + 3], c[4 * b + 4], c[4 * b + 5], c[4 * b + 6]};
+        acc = ghash_absorb(acc, a.h, e);
+      }
+      const uint32_t e4[4] = {c[15], 0, 0, 0};
+      acc = ghash_absorb(acc, a.h, e4);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+  }
+
+  // the wave's CRC stands at the end of its sub-tile in the workgroup's last tile: to the axis's end
+  {
+    for (int k = wave; k < 3; ++k) crc = tab4(lt.sh4k, crc);
+    const uint64_t last = blockIdx.x + (a.ntiles - 1 - blockIdx.x) / gridDim.x * gridDim.x;
+    uint64_t e = a.ntiles - 1 - last;
+    for (int b = 0; e; ++b, e >>= 1)
+      if (e & 1) crc = mat_apply(lt.tile_pow2[b], crc, lane);
+    if (lane == 0) wacc[wave] = crc;
+  }
+  ghash_wg_partial(acc, a.tree, wave_part, a.part);  // its barrier orders wacc too
+  if (threadIdx.x == 0) a.part_crc[blockIdx.x] = wacc[0] ^ wacc[1] ^ wacc[2] ^ wacc[3];
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -2934,6 +3105,48 @@ hipError_t launch_sse_read_range(const SseReadRangeLaunch& a, const DevCrcTables
       r.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(sse_read_range_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_sse_write_fused{-1};
+// -1 = DFS_SSE_WRITE_FUSED_MIN_BYTES, else kSseWriteFusedMinBytes
+static std::atomic<int64_t> g_sse_write_min_bytes{-1};
+
+void set_sse_write_fused(bool on, int64_t min_bytes) {
+  g_sse_write_fused.store(on ? 1 : 0);
+  if (min_bytes >= 0) g_sse_write_min_bytes.store(min_bytes);
+}
+
+void reset_sse_write_fused() {
+  g_sse_write_fused.store(-1);
+  g_sse_write_min_bytes.store(-1);
+}
+
+uint64_t sse_write_fused_min_bytes() {
+  int64_t v = g_sse_write_min_bytes.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_WRITE_FUSED_MIN_BYTES");
+    g_sse_write_min_bytes.store(v = e && std::atoll(e) >= 0 ? std::atoll(e) : static_cast<int64_t>(kSseWriteFusedMinBytes));
+  }
+  return static_cast<uint64_t>(v);
+}
+
+bool sse_write_fused_enabled(bool nvme_sync) {
+  int v = g_sse_write_fused.load();
+  if (v < 0) {  // 0 off, 1 on, 2 (nothing said): on where it measured faster
+    const char* e = std::getenv("DFS_SSE_WRITE_FUSED");
+    g_sse_write_fused.store(v = !e ? 2 : std::atoi(e) == 0 ? 0 : 1);
+  }
+  return v == 1 || (v == 2 && !nvme_sync);
+}
+
+hipError_t launch_sse_write(const SseWriteLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const gcm::Plan p = gcm::plan_for(kSseReadTileBytes * sse_read_tiles(a.n));
+  if (!t || !a.buf || !a.dst || !a.meta || !a.meta_host || !a.part || !a.part_crc || a.n == 0 ||
+      p.nblocks > 0xFFFFFFFEull || reinterpret_cast<uintptr_t>(a.buf) % 16 || reinterpret_cast<uintptr_t>(a.dst) % 16 ||
+      reinterpret_cast<uintptr_t>(a.part) % 16 || a.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sse_write_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
   return hipGetLastError();
 }
 

@@ -1612,19 +1612,18 @@ bool S3Front::native_put(Conn* c, Req& r, const std::string& path, bool part) {
   const uint64_t stored = sse ? n + 28 : n;
   std::map<std::string, std::string> attrs;
   std::string plain_md5, dk;
+  bool sealed = false;  // op 13 stored the object: only the bookkeeping below is left
+  FastClient::Times t;
+  std::string msg, md5;
+  int reps = 0;
+  std::string n1;
   if (sse) {
     // SseManager.encrypt_object (reference auth/sse.rs:10-62): a fresh DEK encrypts the
     // object in place, the KEK wraps the DEK; the ETag stays the plaintext's MD5
     plain_md5 = crypto::md5_hex(dst + 12, n);
     dk = crypto::random_bytes(32);
-    const std::string n1 = crypto::random_bytes(12), n2 = crypto::random_bytes(12);
-    std::memcpy(dst, n1.data(), 12);
-    // the body's AES-GCM on the co-located chunkserver's GPU when it takes it, else here: same bytes
-    if (n && sse_offload() &&
-        fc_->sse_crypt(slot, 12, n, reinterpret_cast<const uint8_t*>(dk.data()), dst, true, dst + 12 + n, r.rid) == FastClient::Ok)
-      st_.sse_offloaded++;
-    else
-      crypto::aes256gcm_encrypt_inplace(reinterpret_cast<const uint8_t*>(dk.data()), dst, dst + 12, n, dst + 12 + n);
+    n1 = crypto::random_bytes(12);
+    const std::string n2 = crypto::random_bytes(12);
     const std::string wrapped = n2 + crypto::aes256gcm_encrypt(cfg_.sse_kek, n2, dk, "");
     attrs["x-amz-sse-encrypted-dek"] = crypto::base64_encode(wrapped);
   }
@@ -1635,12 +1634,49 @@ bool S3Front::native_put(Conn* c, Req& r, const std::string& path, bool part) {
     if (const std::string* ct = r.get("content-type")) attrs["Content-Type"] = *ct;
     attrs["ETag"] = sse ? "\"" + plain_md5 + "\"" : "";
   }
-  FastClient::Times t;
-  std::string msg, md5;
-  int reps = 0;
+  if (sse) {
+    const uint8_t* key = reinterpret_cast<const uint8_t*>(dk.data());
+    // first the whole PUT where it is stored: the chunkserver's GPU encrypts, authenticates, checksums
+    // and lands the slot in one kernel (fast-path op 13), and nothing here hashes the ciphertext
+    if (n && !part && sse_offload()) {
+      const uint8_t* nonce = reinterpret_cast<const uint8_t*>(n1.data());
+      std::string m13;
+      bool spent = false;
+      auto st13 = fc_->sse_write_slot(path, slot, n + 28, key, nonce, plain_md5, &reps, &m13, &t, r.rid, &attrs, &spent);
+      // _put_replace, but only while the slot still holds the plaintext: CreateFile refuses an
+      // existing key before op 13 runs. CompleteFile refuses one too (a concurrent PUT of the key
+      // completed in between), and then the slot is the blob: a second op 13 over it would apply
+      // the same keystream again and store the plaintext.
+      if (st13 == FastClient::Failed && !spent && m13.find("already exists") != std::string::npos) {
+        std::string dmsg;
+        if (fc_->remove(path, &dmsg, r.rid) != FastClient::NotHandled)
+          st13 = fc_->sse_write_slot(path, slot, n + 28, key, nonce, plain_md5, &reps, &m13, &t, r.rid, &attrs, &spent);
+      }
+      // any other Failed with the slot untouched goes on to the present code, which reports it
+      if (st13 == FastClient::Failed && spent) {  // nothing to hand over: the plaintext is gone from the slot
+        r.keep_alive = false;
+        s3_error(c, r, 500, "InternalError", m13.empty() ? "write failed" : m13, path);
+        return false;
+      }
+      if (st13 == FastClient::Ok) {
+        sealed = true;
+        std::lock_guard<std::mutex> g(st_mu_);
+        st_.sse_offloaded++;
+      }
+    }
+    if (!sealed) {
+      std::memcpy(dst, n1.data(), 12);
+      // the body's AES-GCM on the co-located chunkserver's GPU when it takes it, else here: same bytes
+      if (n && sse_offload() && fc_->sse_crypt(slot, 12, n, key, dst, true, dst + 12 + n, r.rid) == FastClient::Ok)
+        st_.sse_offloaded++;
+      else
+        crypto::aes256gcm_encrypt_inplace(key, dst, dst + 12, n, dst + 12 + n);
+    }
+  }
   // without SSE the ETag attribute is the MD5 the write computes of the stored bytes
   const char* etag_attr = part || sse ? nullptr : "ETag";
-  auto st = fc_->write_slot(path, slot, stored, &reps, &msg, &t, r.rid, part ? nullptr : &attrs, etag_attr, &md5);
+  auto st = sealed ? FastClient::Ok
+                   : fc_->write_slot(path, slot, stored, &reps, &msg, &t, r.rid, part ? nullptr : &attrs, etag_attr, &md5);
   if (st == FastClient::Failed && msg.find("already exists") != std::string::npos) {
     // _put_replace: an existing key is replaced (delete, then create again)
     std::string dmsg;

@@ -133,6 +133,21 @@ class FastPathClient:
         st, _total, n, _msg = self._call(11 if length is None else 12, body)
         return st, n if st == OK else 0
 
+    def sse_write(self, block_id: str, shm_path: str, shm_off: int, length: int, key: bytes, nonce: bytes, term: int,
+                  next_servers: list[str] | tuple = (), request_id: str | None = None):
+        """PUT of an SSE-S3 object by one kernel on the chunkserver's GPU (csrc/fastpath.cpp op 13): the
+        arena holds [12 free][plaintext][16 free], ``length`` bytes in all, at ``shm_off`` and afterwards
+        the blob [nonce][ciphertext][tag], stored as ``block_id`` and fanned out to ``next_servers`` as
+        ``write`` does. Returns (status, replicas_written, crc of the blob): OK, FENCED, IO_ERROR, or
+        UNSUPPORTED, with the arena untouched, when the kernel would not take it (the caller then
+        encrypts and writes its own way)."""
+        body = struct.pack("<QQQ", term, shm_off, length) + _s(block_id.encode()) + _s(shm_path.encode())
+        body += _s(key) + _s(nonce)
+        body += struct.pack("<H", len(next_servers)) + b"".join(_s(a.encode()) for a in next_servers)
+        body += _s(self._rid(request_id))
+        st, _total, replicas, msg = self._call(13, body)
+        return st, replicas if st == OK else 0, int(msg, 16) if st == OK else 0
+
     @staticmethod
     def _rid(request_id: str | None) -> bytes:
         from .rpc import current_request_id

@@ -259,6 +259,10 @@ PYBIND11_MODULE(_dfs_native, m) {
         py::arg("on"), py::arg("min_bytes") = -1);
   m.def("reset_sse_write_fused", &reset_sse_write_fused, "route and floor back to the environment's and the defaults'");
   m.def("sse_write_fused_min_bytes", &sse_write_fused_min_bytes, "bodies below this many bytes stay staged");
+  m.def("set_sse_copy_fused", &set_sse_copy_fused,
+        "CopyObjects of SSE-S3 objects verified, re-keyed, checksummed and landed by one kernel (else sse_read, then sse_write)",
+        py::arg("on"), py::arg("min_bytes") = -1);
+  m.def("sse_copy_fused_min_bytes", &sse_copy_fused_min_bytes, "blobs with less plaintext than this stay staged");
   // the shape of an sse_read_kernel launch: bytes of the blob per workgroup step, and the grid's cap
   m.attr("sse_read_tile_bytes") = kSseReadTileBytes;
   m.attr("sse_read_max_grid") = static_cast<int>(gcm::kGcmMaxGrid);
@@ -606,6 +610,30 @@ PYBIND11_MODULE(_dfs_native, m) {
         const uint64_t len = static_cast<uint64_t>(bi.size * bi.itemsize);
         return len >= 29 && s.sse_write_fusable(static_cast<const uint8_t*>(bi.ptr), len - 28);
       }, py::arg("buffer"))
+      // CopyObject of an SSE-S3 object: block `src_id` under key_src becomes block `dst_id` under
+      // (key_dst, nonce_dst), stored as write() would store OpenSSL's blob. One kernel, HBM to HBM, when
+      // the source is resident. Returns (status, crc of the new blob or the bad slice, error): 0 Ok,
+      // 1 NotFound, 2 Corrupt, 3 AuthFailed, 4 IoError.
+      .def("sse_copy", [](ChunkStore& s, const std::string& src_id, const std::string& dst_id, py::bytes key_src,
+                          py::bytes key_dst, py::bytes nonce_dst, bool persist_now) {
+        std::string ks = key_src, kd = key_dst, nc = nonce_dst;
+        if (ks.size() != 32 || kd.size() != 32 || nc.size() != 12)
+          throw std::invalid_argument("sse_copy: two 32-byte keys and a 12-byte nonce");
+        ChunkStore::SseCopyResult r;
+        int64_t bad = -1;
+        {
+          py::gil_scoped_release rel;
+          r = s.sse_copy(src_id, dst_id, reinterpret_cast<const uint8_t*>(ks.data()),
+                         reinterpret_cast<const uint8_t*>(kd.data()), reinterpret_cast<const uint8_t*>(nc.data()),
+                         persist_now, false, nullptr, &bad);
+        }
+        gcm::wipe(&ks[0], ks.size());
+        gcm::wipe(&kd[0], kd.size());
+        return py::make_tuple(static_cast<int>(r.status),
+                              r.status == ChunkStore::SseRead::Corrupt ? static_cast<uint64_t>(bad) : r.actual_crc, r.error);
+      }, py::arg("src_id"), py::arg("dst_id"), py::arg("key_src"), py::arg("key_dst"), py::arg("nonce_dst"),
+         py::arg("persist_now") = true)
+      .def("sse_copy_fusable", &ChunkStore::sse_copy_fusable, py::arg("src_id"), py::arg("dst_id"))
       // degraded read: bytes [offset, offset + length) of the RS(k, m) file whose k + m shards are
       // the resident blocks `block_ids` ("" = lost) into `out`; a registered `out` takes the
       // single-kernel path. Returns the number of bytes placed, None on failure.

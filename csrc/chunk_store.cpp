@@ -2566,6 +2566,7 @@ StoreStats ChunkStore::stats() {
   s.sse_fused_reads = sse_fused_reads_.load();
   s.sse_fused_range_reads = sse_fused_range_reads_.load();
   s.sse_fused_writes = sse_fused_writes_.load();
+  s.sse_fused_copies = sse_fused_copies_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -4463,6 +4464,226 @@ WriteResult ChunkStore::sse_write(const std::string& id, const uint8_t key[32], 
   std::memcpy(buf, nonce, 12);
   if (!sse_crypt(buf + 12, n, key, nonce, true, buf + 12 + n, &res.error)) return res;
   return persist_now ? write(id, buf, size, 0) : stage(id, buf, size, 0);
+}
+
+namespace {
+// The lane's pinned scratch of an sse_rekey_kernel launch: the GHASH partials of either side, verdicts,
+// CRC partials, the source's nonce and tag, the bytes of the slices that hold the new tag, .meta image.
+constexpr uint64_t kSseCopyPartDstOff = gcm::kGcmMaxGrid * sizeof(gcm::U128);
+constexpr uint64_t kSseCopyBadOff = 2 * kSseCopyPartDstOff;
+constexpr uint64_t kSseCopyCrcOff = kSseCopyBadOff + gcm::kGcmMaxGrid * sizeof(uint32_t);
+constexpr uint64_t kSseCopyNonceTagOff = kSseCopyCrcOff + gcm::kGcmMaxGrid * sizeof(uint32_t);
+constexpr uint64_t kSseCopyTailOff = kSseCopyNonceTagOff + 32;
+constexpr uint64_t kSseCopyMetaOff = kSseCopyTailOff + kSseRekeyTailBytes;
+static_assert(kSseCopyTailOff % 16 == 0 && kSseCopyMetaOff % 16 == 0, "vector stores into the scratch");
+}  // namespace
+
+// The source pinned where it lies when sse_rekey_kernel would take the copy (the caller unpins), else
+// null. Unlike a read, a copy does not promote: a source that has left HBM takes the staged route.
+const uint8_t* ChunkStore::sse_copy_pin(const std::string& src_id, const std::string& dst_id, uint64_t* size) {
+  if (!gpu() || !sse_copy_fused_enabled() || !crc_mfma_enabled() || !dtables_ || src_id == dst_id) return nullptr;
+  std::lock_guard<std::mutex> g(mu_);
+  auto it = index_.find(src_id);
+  if (it == index_.end() || it->second.dev_off < 0) return nullptr;
+  Block& b = it->second;
+  if (b.size < 29 || b.size - 28 < sse_copy_fused_min_bytes() || sse_read_tiles(b.size - 28) > (0xFFFFFFFEull >> 10))
+    return nullptr;
+  b.pins++;
+  touch_locked(src_id, b);
+  *size = b.size;
+  return arena_ + b.dev_off;
+}
+
+bool ChunkStore::sse_copy_fusable(const std::string& src_id, const std::string& dst_id) {
+  uint64_t size = 0;
+  if (!sse_copy_pin(src_id, dst_id, &size)) return false;
+  unpin(src_id);
+  return true;
+}
+
+ChunkStore::SseCopyResult ChunkStore::sse_copy(const std::string& src_id, const std::string& dst_id,
+                                               const uint8_t key_src[32], const uint8_t key_dst[32],
+                                               const uint8_t nonce_dst[12], bool persist_now, bool fused_only,
+                                               bool* declined, int64_t* bad_slice) {
+  TraceRange tr("dfs.store.sse_copy");  // no key material in ranges, logs or errors
+  if (declined) *declined = false;
+  if (bad_slice) *bad_slice = -1;
+  SseCopyResult res;
+  res.status = SseRead::IoError;
+  if (!valid_block_id(dst_id)) {
+    static_cast<WriteResult&>(res) = bad_id(dst_id);
+    return res;
+  }
+  uint64_t size = 0;
+  const uint8_t* d = sse_copy_pin(src_id, dst_id, &size);
+  DevExtent ext;
+  if (d) {
+    HIP_OK(hipSetDevice(cfg_.device));
+    ext = reserve(size);
+    if (ext.off < 0) {  // the arena is full and nothing has been done: the staged route, like any other case
+      unpin(src_id);
+      d = nullptr;
+    }
+  }
+  if (d) {
+    const uint64_t n = size - 28, S = num_slices(size), s_body = sse_write_body_slices(n), ntiles = sse_read_tiles(n);
+    const gcm::Plan plan = gcm::plan_for(kSseReadTileBytes * ntiles);
+    auto* dmeta = reinterpret_cast<uint32_t*>(ext.ptr + align_up(size, 256));
+    Lane* l = acquire_lane();
+    ensure_hscratch(l, kSseCopyMetaOff + S * 4 + 16);
+    auto* hmeta = reinterpret_cast<uint32_t*>(l->hscratch + kSseCopyMetaOff);
+    // Nothing below throws: the lane and the pin are released and every copy of either key schedule
+    // and of the powers of either H that the store owns is wiped on each way out. A launch that
+    // fails has written nothing, so the call goes on to the staged route; a failure after it is an
+    // error. The extent is named by no block until the source has verified and authenticated.
+    gcm::Keys ks, kd;
+    SseRekeyLaunch a{};
+    hipError_t launched = hipErrorNotReady, done = hipSuccess;
+    uint32_t bad = 0xFFFFFFFFu, block_crc = 0;
+    bool authentic = false;
+    auto meta = std::make_shared<std::vector<uint8_t>>();
+    if (l->hscratch_dev && gcm::prepare_keyed(key_src, plan, &ks) && gcm::prepare(key_dst, nonce_dst, plan, &kd)) {
+      uint8_t* hdev = static_cast<uint8_t*>(l->hscratch_dev);
+      a.src = d;
+      a.src_meta = reinterpret_cast<const uint32_t*>(d + align_up(size, 256));
+      a.dst = ext.ptr;
+      a.meta = dmeta;
+      a.meta_host = reinterpret_cast<uint32_t*>(hdev + kSseCopyMetaOff);
+      a.n = n;
+      a.ntiles = ntiles;
+      a.full_init = crc_init_term(kSliceBytes);
+      a.tail_init = size % kSliceBytes ? crc_init_term(size % kSliceBytes) : 0;
+      std::memcpy(a.nonce, kd.nonce, sizeof(a.nonce));
+      std::memcpy(a.from.rk, ks.rk, sizeof(a.from.rk));
+      a.from.h = ks.h;
+      a.from.hjump = gcm::write_jump(ks, plan);
+      std::memcpy(a.from.tree, ks.tree, sizeof(a.from.tree));
+      a.from.part = reinterpret_cast<gcm::U128*>(hdev);
+      std::memcpy(a.to.rk, kd.rk, sizeof(a.to.rk));
+      a.to.h = kd.h;
+      a.to.hjump = gcm::write_jump(kd, plan);
+      std::memcpy(a.to.tree, kd.tree, sizeof(a.to.tree));
+      a.to.part = reinterpret_cast<gcm::U128*>(hdev + kSseCopyPartDstOff);
+      a.part_bad = reinterpret_cast<uint32_t*>(hdev + kSseCopyBadOff);
+      a.part_crc = reinterpret_cast<uint32_t*>(hdev + kSseCopyCrcOff);
+      a.nonce_tag = hdev + kSseCopyNonceTagOff;
+      a.tail_host = hdev + kSseCopyTailOff;
+      launched = launch_sse_rekey(a, dtables_, plan.grid, l->stream);
+      if (launched == hipSuccess) {
+        launches_++;
+        // H_dst^-vback needs only the key: computed while the kernel runs
+        const uint64_t vback = plan.nblocks - (n + 15) / 16;
+        gcm::U128 factor = gcm::unfold_factor(kd, vback);
+        done = hipStreamSynchronize(l->stream);
+        if (done == hipSuccess) {
+          for (int g = 0; g < plan.grid; ++g)
+            bad = std::min(bad, reinterpret_cast<const uint32_t*>(l->hscratch + kSseCopyBadOff)[g]);
+          // the source first: its slices, then its tag under the nonce the kernel read from it
+          const uint8_t* nt = l->hscratch + kSseCopyNonceTagOff;
+          authentic = bad == 0xFFFFFFFFu && gcm::set_nonce(key_src, nt, &ks) &&
+                      gcm::tag_matches(ks, gcm::ghash_fold(ks, plan, reinterpret_cast<const gcm::U128*>(l->hscratch)), n,
+                                       vback, nt + 12);
+        }
+        if (done == hipSuccess && authentic) {
+          // the destination's tag, into the host's copy of its last slices and from there into the extent
+          uint8_t* tail = l->hscratch + kSseCopyTailOff;
+          const uint64_t rest = size - s_body * kSliceBytes, tag_at = 12 + n - s_body * kSliceBytes;
+          const gcm::U128 sum = gcm::unfold(
+              gcm::ghash_fold(kd, plan, reinterpret_cast<const gcm::U128*>(l->hscratch + kSseCopyPartDstOff)), factor);
+          gcm::finish_tag(kd, sum, n, tail + tag_at);
+          done = hipMemcpyAsync(ext.ptr + 12 + n, tail + tag_at, 16, hipMemcpyHostToDevice, l->stream);
+          // the slices that hold tag bytes: their .meta words and the block CRC's end
+          crc32_slices(tail, rest, hmeta + s_body);
+          uint32_t r = 0;
+          for (int g = 0; g < plan.grid; ++g) r ^= reinterpret_cast<const uint32_t*>(l->hscratch + kSseCopyCrcOff)[g];
+          r = crc_unshift(r, ntiles * kSseReadTileBytes - s_body * kSliceBytes);
+          r = crc_shift(r, rest) ^ crc32(tail, rest) ^ crc_init_term(rest);
+          block_crc = r ^ crc_init_term(size);
+          for (uint64_t i = s_body; i < S; ++i) hmeta[i] = __builtin_bswap32(hmeta[i]);
+          if (done == hipSuccess)
+            done = hipMemcpyAsync(dmeta + s_body, hmeta + s_body, (S - s_body) * 4, hipMemcpyHostToDevice, l->stream);
+          if (done == hipSuccess) done = hipStreamSynchronize(l->stream);
+          meta->assign(reinterpret_cast<const uint8_t*>(hmeta), reinterpret_cast<const uint8_t*>(hmeta) + S * 4);
+        }
+        gcm::wipe(&factor, sizeof(factor));
+        gcm::wipe(l->hscratch, 2 * kSseCopyPartDstOff);
+      }
+    }
+    gcm::wipe(&a, sizeof(a));
+    gcm::wipe(&ks, sizeof(ks));
+    gcm::wipe(&kd, sizeof(kd));
+    release_lane(l);
+    unpin(src_id);
+    if (launched == hipSuccess) {
+      if (done != hipSuccess) {
+        release(ext);
+        res.error = std::string("SSE copy kernel: ") + hipGetErrorString(done);
+        return res;
+      }
+      if (!authentic) {  // block dst_id never exists
+        release(ext);
+        if (bad != 0xFFFFFFFFu) {
+          std::lock_guard<std::mutex> g(mu_);
+          ++st_.crc_mismatches;
+          if (bad_slice) *bad_slice = bad;
+          res.error = "Checksum mismatch at chunk " + std::to_string(bad);
+          res.status = SseRead::Corrupt;
+          return res;
+        }
+        res.error = kSseAuthFailed;
+        res.status = SseRead::AuthFailed;
+        return res;
+      }
+      res.actual_crc = block_crc;
+      // the durable copy as commit_device makes it for a device extent, without its checksum pass:
+      // the kernel and the lines above produced .meta and the block CRC
+      const bool sync_now = persist_now && cfg_.durability == Durability::NvmeSync;
+      JournalRec jr;
+      const bool jok = sync_now && journal_takes(size, S);
+      std::unique_ptr<FileClaim> claim;
+      if (sync_now && !jok && journal_) claim = std::make_unique<FileClaim>(this, dst_id);
+      if (jok ? !journal_block(dst_id, nullptr, ext.ptr, size, block_crc, *meta, &jr, &res.error)
+              : sync_now && (!persist_from_device(dst_id, ext.ptr, size, meta->data(), S, &res.error) ||
+                             !supersede_file(dst_id, &res.error))) {
+        release(ext);
+        return res;
+      }
+      insert_resident(dst_id, ext, size, block_crc, sync_now && !jok, meta, 0, jok ? &jr : nullptr);
+      sse_fused_copies_++;  // a copy that landed: refused sources and failed commits do not count
+      res.ok = true;
+      res.status = SseRead::Ok;
+      return res;
+    }
+    (void)hipGetLastError();
+    release(ext);
+  }
+  const int64_t have = block_size(src_id);
+  if (have < 0) {
+    res.error = "Block not found";
+    res.status = SseRead::NotFound;
+    return res;
+  }
+  if (fused_only) {
+    if (declined) *declined = true;
+    res.error = "the kernel does not take this copy";
+    res.status = SseRead::Declined;
+    return res;
+  }
+  // staged: sse_read of the plaintext into a temporary laid out as a PUT's slot, then sse_write of it
+  // under the new key, each on its own staged route (the temporary is not registered)
+  if (have < 29) {
+    res.error = "not an SSE blob: " + std::to_string(have) + " bytes";
+    return res;
+  }
+  std::vector<uint8_t> tmp(static_cast<uint64_t>(have));
+  uint64_t n = 0;
+  res.status = sse_read(src_id, key_src, tmp.data() + 12, tmp.size() - 28, &n, &res.error, bad_slice);
+  if (res.status == SseRead::Ok) {
+    static_cast<WriteResult&>(res) = sse_write(dst_id, key_dst, nonce_dst, tmp.data(), n, persist_now);
+    if (!res.ok) res.status = SseRead::IoError;
+  }
+  gcm::wipe(tmp.data(), tmp.size());
+  return res;
 }
 
 bool ChunkStore::device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n) {

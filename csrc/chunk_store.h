@@ -99,6 +99,7 @@ struct StoreStats {
   uint64_t sse_fused_reads = 0;   // stored SSE blobs verified, decrypted and delivered by one sse_read_kernel launch
   uint64_t sse_fused_range_reads = 0;  // of those, byte ranges by sse_read_range_kernel
   uint64_t sse_fused_writes = 0;  // SSE PUTs encrypted, authenticated, checksummed and landed by one sse_write_kernel launch
+  uint64_t sse_fused_copies = 0;  // SSE CopyObjects verified, re-keyed, checksummed and landed by one sse_rekey_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -367,6 +368,28 @@ class ChunkStore {
   bool sse_write_fusable(const uint8_t* buf, uint64_t n);  // would sse_write take the kernel
   WriteResult sse_write(const std::string& id, const uint8_t key[32], const uint8_t nonce[12], uint8_t* buf, uint64_t n,
                         bool persist_now = true, bool fused_only = false, bool* declined = nullptr);
+  // A CopyObject of an SSE-S3 object: block `src_id` holds [nonce 12][ciphertext n][tag 16] under
+  // key_src; afterwards block `dst_id` holds the same plaintext under (key_dst, nonce_dst), stored
+  // exactly as write(dst_id, blob, n + 28, 0) would have stored OpenSSL's blob: same bytes, .meta,
+  // block CRC, journal or files; the result carries that CRC and a status as sse_read's. On a GPU
+  // store with the source resident in HBM (it is pinned for the call, never promoted), n at or above
+  // sse_copy_fused_min_bytes(), the route on and src_id != dst_id: one extent, one
+  // sse_rekey_kernel launch that verifies and authenticates the source and re-keys, authenticates,
+  // checksums and lands the destination, then the host's verdict on the source and, only if it
+  // holds, the new tag, its slices' checksums and the commit, the durable copy made from device
+  // memory as commit_device makes it. No payload crosses the host link. Corrupt (sets *bad_slice,
+  // counts in crc_mismatches) and AuthFailed release the extent: dst_id never exists. Otherwise the
+  // staged route (a full arena and a failed launch take it too): sse_read into a temporary, then
+  // sse_write from it; same bytes, same statuses. sse_fused_copies counts the copies that landed. With
+  // fused_only the call declines (status Declined, *declined set, nothing done) instead. Every copy
+  // of both key schedules and all powers of either H is wiped before this returns.
+  struct SseCopyResult : WriteResult {
+    SseRead status = SseRead::IoError;
+  };
+  bool sse_copy_fusable(const std::string& src_id, const std::string& dst_id);  // would sse_copy take the kernel
+  SseCopyResult sse_copy(const std::string& src_id, const std::string& dst_id, const uint8_t key_src[32],
+                         const uint8_t key_dst[32], const uint8_t nonce_dst[12], bool persist_now = true,
+                         bool fused_only = false, bool* declined = nullptr, int64_t* bad_slice = nullptr);
   // Device bytes into host memory (registered: one DMA) and synchronously complete.
   bool device_to_host(uint8_t* dst, const uint8_t* src_dev, uint64_t n);
   // A copy of device bytes committed as block `id` (checksummed, verified, made durable).
@@ -571,7 +594,8 @@ class ChunkStore {
                 std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
   const uint8_t* sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size, uint64_t from, uint64_t want);
   std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0},
-      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0}, sse_fused_writes_{0};
+      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0}, sse_fused_writes_{0}, sse_fused_copies_{0};
+  const uint8_t* sse_copy_pin(const std::string& src_id, const std::string& dst_id, uint64_t* size);
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;
   IoPool io_{8, 30000, "store-io"};  // data-file writes and .meta flushes beside the GPU staging (no per-write threads)

@@ -891,6 +891,131 @@ FastClient::Status FastClient::sse_read(const std::string& meta_pb, const uint8_
   return Ok;
 }
 
+FastClient::Status FastClient::sse_copy(const std::string& src_meta_pb, const std::string& path, const uint8_t key_src[32],
+                                        const uint8_t key_dst[32], const uint8_t nonce[12], const std::string& etag_md5,
+                                        std::string* msg, const std::string& rid_in,
+                                        const std::map<std::string, std::string>* attrs, bool* spent) {
+  bool own = false;
+  if (!spent) spent = &own;
+  *spent = false;
+  const std::string rid = rid_in.empty() ? new_request_id() : rid_in;
+  RequestScope rs(rid);
+  TraceRange tr("dfs.client.sse_copy");
+  pb::FileMetadata m;
+  if (!m.decode(src_meta_pb) || m.blocks.size() != 1 || m.blocks[0].ec_data_shards > 0 || m.size < 29) return NotHandled;
+  const pb::BlockInfo& b = m.blocks[0];
+  bool local = false;
+  for (auto& l : b.locations) local |= strip_scheme(l) == local_cs_;
+  if (!local) return NotHandled;
+  std::string sock = master_socket(path);
+  if (sock.empty()) return NotHandled;
+
+  pb::CreateFileRequest creq;
+  creq.path = path;
+  creq.allocate_block = true;
+  creq.defer_create = true;
+  creq.preferred_chunk_server = local_cs_;
+  int code;
+  std::string raw;
+  if (!call(sock, "/dfs.MasterService/CreateFile", rid, creq.str(), &code, &raw)) return NotHandled;
+  if (code == kOutOfRange || code == kFailedPrecondition || code == kUnavailable) return NotHandled;
+  if (code != 0) {
+    *msg = "Failed to create file: " + raw;
+    return Failed;
+  }
+  pb::CreateFileResponse cresp;
+  if (!cresp.decode(raw)) return NotHandled;
+  if (!cresp.success) {
+    if (cresp.error_message == "Not Leader") return NotHandled;
+    *msg = "Failed to create file: " + cresp.error_message;
+    return Failed;
+  }
+  if (!cresp.has_allocation || !cresp.allocation.has_block) return NotHandled;
+  const pb::AllocateBlockResponse& alloc = cresp.allocation;
+  if (alloc.chunk_server_addresses.empty()) {
+    *msg = "No chunk servers available";
+    return Failed;
+  }
+  if (!cresp.deferred || strip_scheme(alloc.chunk_server_addresses[0]) != local_cs_)
+    return NotHandled;  // nothing was recorded yet: the caller's own route redoes it
+
+  std::string body;
+  put<uint64_t>(body, alloc.master_term);
+  put_str(body, b.block_id);
+  put_str(body, alloc.block.block_id);
+  put_str(body, arena_path_);
+  put<uint16_t>(body, 32);  // straight into `body`, which is wiped: no temporary holds a key
+  body.append(reinterpret_cast<const char*>(key_src), 32);
+  put<uint16_t>(body, 32);
+  body.append(reinterpret_cast<const char*>(key_dst), 32);
+  put<uint16_t>(body, 12);
+  body.append(reinterpret_cast<const char*>(nonce), 12);
+  put<uint16_t>(body, static_cast<uint16_t>(alloc.chunk_server_addresses.size() - 1));
+  for (size_t i = 1; i < alloc.chunk_server_addresses.size(); ++i)
+    put_str(body, strip_scheme(alloc.chunk_server_addresses[i]));
+  put_str(body, rid);
+  uint8_t st;
+  uint64_t total, written;
+  std::string fmsg;
+  bool reached = false;
+  const bool sent = fp_call(14, body, &st, &total, &written, &fmsg, &reached);
+  gcm::wipe(&body[0], body.size());
+  // An op 14 lost on a connection that stood may have reached the server, which may store the block
+  // now or later: the copy counts as spent. Only a connection that never stood is NotHandled.
+  if (!sent && reached) {
+    *spent = true;
+    *msg = "Failed to copy block: fast path connection lost";
+    return Failed;
+  }
+  if (!sent) return NotHandled;
+  if (st == 5 || st == 4 || st == 9) {  // fenced, I/O error, or a source that does not authenticate: final
+    *spent = st == 4;
+    *msg = "Failed to copy block: " + fmsg;
+    return Failed;
+  }
+  if (st != 0) return NotHandled;  // op 14 answers these only while nothing has been done
+  *spent = true;
+  char* end = nullptr;
+  const uint32_t crc = static_cast<uint32_t>(std::strtoul(fmsg.c_str(), &end, 16));
+  if (fmsg.size() != 8 || *end) {
+    *msg = "Failed to copy block: malformed checksum in the reply";
+    return Failed;
+  }
+  sse_gpu_++;
+
+  pb::CompleteFileRequest done;
+  done.path = path;
+  done.size = m.size;
+  done.etag_md5 = etag_md5;
+  done.created_at_ms = static_cast<uint64_t>(now_ms());
+  pb::BlockChecksumInfo sum;
+  sum.block_id = alloc.block.block_id;
+  sum.checksum_crc32c = crc;
+  sum.actual_size = m.size;
+  done.block_checksums.push_back(sum);
+  done.create = true;
+  done.ec_data_shards = alloc.ec_data_shards;
+  done.ec_parity_shards = alloc.ec_parity_shards;
+  done.blocks.push_back(alloc.block);
+  if (attrs) done.attributes = *attrs;
+  if (!call(sock, "/dfs.MasterService/CompleteFile", rid, done.str(), &code, &raw)) {
+    *msg = "Failed to complete file: master connection lost";
+    return Failed;
+  }
+  if (code != 0) {
+    *msg = "Failed to complete file: " + raw;
+    return Failed;
+  }
+  pb::CompleteFileResponse dresp;
+  dresp.decode(raw);
+  if (!dresp.success) {
+    *msg = dresp.error_message.empty() ? "Failed to complete file" : "Failed to create file: " + dresp.error_message;
+    return Failed;
+  }
+  writes_++;
+  return Ok;
+}
+
 FastClient::Status FastClient::write_ec(const std::string& path, const uint8_t* data, size_t n, int k, int m,
                                         std::string* msg, const std::string& rid_in) {
   const std::string rid = rid_in.empty() ? new_request_id() : rid_in;

@@ -153,6 +153,18 @@ class FastClient {
   // bytes into the slot (0 for the whole object).
   Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
                   uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr);
+  // CopyObject of the stored SSE-S3 blob that `src_meta_pb` describes (one block on the co-located
+  // chunkserver) to `path`, sealed where it is stored and with no slot: CreateFile for the destination,
+  // fast-path op 14 on the source's block (one kernel there verifies, authenticates and re-keys it under
+  // (key_dst, nonce) into the new block, HBM to HBM), CompleteFile with the CRC from the reply and
+  // `etag_md5`, the plaintext's MD5 that the source's ETag already is. The contract of sse_write_slot:
+  // NotHandled, nothing has been done and the caller copies its own way; Failed with *spent set came
+  // after the op was sent (IoError, a lost connection, a malformed reply, CompleteFile) and the copy
+  // must not be repeated blindly; Failed without it came from CreateFile, a fence, or a source whose
+  // tag does not match, which is final.
+  Status sse_copy(const std::string& src_meta_pb, const std::string& path, const uint8_t key_src[32],
+                  const uint8_t key_dst[32], const uint8_t nonce[12], const std::string& etag_md5, std::string* msg,
+                  const std::string& rid, const std::map<std::string, std::string>* attrs, bool* spent = nullptr);
   uint64_t sse_gpu_ops() const { return sse_gpu_.load(); }
   uint64_t ec_gpu_ops() const { return ec_gpu_.load(); }
   uint64_t ec_cpu_ops() const { return ec_cpu_.load(); }

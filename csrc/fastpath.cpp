@@ -1061,6 +1061,53 @@ void FastPathServer::serve(int fd) {
       }
       gcm::wipe(&key[0], key.size());
       gcm::wipe(body.data(), body.size());
+    } else if (op == 14) {  // SSE_COPY: a stored SSE-S3 blob re-keyed into a new block by one kernel, HBM to HBM
+      const uint64_t term = rd.get<uint64_t>();
+      std::string src = rd.str(), dst = rd.str(), path = rd.str(), key_src = rd.str(), key_dst = rd.str(), nonce = rd.str();
+      std::vector<std::string> next = read_list(rd, true);
+      std::string rid = rd.p < rd.end ? rd.str() : std::string();
+      RequestScope rs(rid);
+      note_rid(rid);
+      TraceRange tr("dfs.fp.sse_copy");  // the keys stay out of ranges, logs and answers
+      if (!rd.ok || src.empty() || dst.empty() || key_src.size() != 32 || key_dst.size() != 32 || nonce.size() != 12) {
+        sent = send_response(fd, FpStatus::BadRequest, 0, 0, "malformed sse copy request");
+      } else if (fenced(term, &msg)) {
+        sent = send_response(fd, FpStatus::Fenced, term_.load(), 0, msg);
+      } else if (!next.empty() && !(p2p_ready(next) && repl_->transport()->device_buffers())) {
+        // The new block has no client slot behind it, so a replica can only take it from HBM over a
+        // device P2P pair (replicate_one with no ShmSrc, as a mid-chain op 3 forwards): without a pair
+        // that route has no shared-memory fallback and would count a replica failure.
+        sent = send_response(fd, FpStatus::Unsupported, 0, 0, "a replica without a device P2P pair");
+      } else {
+        // the kernel or nothing: declined means that nothing has been done
+        bool declined = false;
+        const ChunkStore::SseCopyResult cr =
+            store_->sse_copy(src, dst, reinterpret_cast<const uint8_t*>(key_src.data()),
+                             reinterpret_cast<const uint8_t*>(key_dst.data()), reinterpret_cast<const uint8_t*>(nonce.data()),
+                             false, true, &declined);
+        if (declined) {
+          sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU, source not resident or below the kernel's floor");
+        } else if (cr.ok) {
+          bump(&FpStats::sse_copies);
+          char hex[9];
+          std::snprintf(hex, sizeof(hex), "%08x", cr.actual_crc);
+          // staged in HBM now: durable here from device memory, and out to the replicas from there
+          // (the engine pins the resident block by its id), as a mid-chain op 3 does
+          const int64_t size = store_->block_size(dst);
+          sent = size < 0 ? send_response(fd, FpStatus::IoError, 0, 0, "the copy vanished before it was persisted")
+                          : persist_and_forward(dst, nullptr, static_cast<uint64_t>(size), cr.actual_crc, term, next, ShmSrc{}, hex);
+        } else {
+          switch (cr.status) {
+            case ChunkStore::SseRead::NotFound: sent = send_response(fd, FpStatus::NotFound, 0, 0, cr.error); break;
+            case ChunkStore::SseRead::Corrupt: sent = send_response(fd, FpStatus::Corrupt, 0, 0, cr.error); break;
+            case ChunkStore::SseRead::AuthFailed: sent = send_response(fd, FpStatus::AuthFailed, 0, 0, cr.error); break;
+            default: sent = send_response(fd, FpStatus::IoError, 0, 0, cr.error); break;
+          }
+        }
+      }
+      gcm::wipe(&key_src[0], key_src.size());
+      gcm::wipe(&key_dst[0], key_dst.size());
+      gcm::wipe(body.data(), body.size());
     } else if (op == 7) {  // EC_WRITE: encode in HBM, scatter the shards over the engine
       sent = ec_write(fd, body.data() + 1, body.data() + n);
     } else if (op == 8) {  // EC_READ: gather the surviving shards into HBM, decode there

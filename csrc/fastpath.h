@@ -60,6 +60,18 @@
 //               Unsupported only while the slot is untouched (ChunkStore::sse_write_fusable says no, a
 //               replica off this host, the arena not mapped or pinned): the client then encrypts and writes
 //               its own way. Fenced, BadRequest (key or nonce length, len < 29), IoError after the launch.
+//     op 14 SSE_COPY: u64 term | u16 src_id | u16 dst_id | u16 path | u16 key_src(32) | u16 key_dst(32) | u16 nonce(12)
+//               [| u16 n_next | (u16 len addr)*] [| u16 rid]  -- CopyObject of an SSE-S3 object by sse_rekey_kernel:
+//               the stored blob `src_id` verified, authenticated, re-keyed under (key_dst, nonce) and stored,
+//               durable, as block `dst_id`, HBM to HBM: no slot is used (`path` only names the client's
+//               arena and may be empty), then persisted from device memory and fanned out to `next` from
+//               HBM as a mid-chain op 3 forwards (replicate with no shared-memory source: the engine pins
+//               the resident block by its id). Answers as op 13, Ok with bytes = replicas written and msg =
+//               the new blob's CRC-32 as 8 hex digits, or as op 11 NotFound, Corrupt or AuthFailed, after
+//               which `dst_id` does not exist. Unsupported only while nothing has been done:
+//               ChunkStore::sse_copy_fusable says no, or some server of `next` has no device P2P pair up
+//               (with no slot there is no shared-memory fallback, so that replica would only be counted
+//               as failed): the client then copies its own way.
 //   response = u32 body_len | u8 status | u64 total | u64 bytes | u16 msg_len msg
 //   (for WRITE/REPL ``bytes`` carries replicas_written; for CTRL ``msg`` is the engine reply)
 //
@@ -110,6 +122,7 @@ struct FpStats {
   uint64_t sse_crypts = 0;        // SSE bodies encrypted or decrypted in clients' slots
   uint64_t sse_reads = 0;         // stored SSE blobs decrypted into clients' slots by one kernel
   uint64_t sse_writes = 0;        // SSE bodies encrypted in clients' slots and stored by one kernel
+  uint64_t sse_copies = 0;        // stored SSE blobs re-keyed into new blocks by one kernel
   uint64_t heals_out = 0, heals_in = 0;  // heal / balancer copies sent / received on the engine
   uint64_t sliced_writes = 0;  // head writes whose replica sends overlapped the staging
   // device-resident erasure coding: EC writes whose shards were encoded and scattered HBM ->

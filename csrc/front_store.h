@@ -95,6 +95,18 @@ class FrontStore {
     if (spent) *spent = false;
     return FastClient::NotHandled;
   }
+  // CopyObject of a stored SSE-S3 blob re-keyed where it is stored (FastClient::sse_copy): no slot and
+  // no payload here. NotHandled, the default (the remote store's too) and whenever nothing has been
+  // done: the caller copies its own way. Failed sets *spent when it came after the op.
+  virtual Status sse_copy(const std::string& src_meta_pb, const std::string& path, const uint8_t key_src[32],
+                          const uint8_t key_dst[32], const uint8_t nonce[12], const std::string& etag_md5,
+                          std::string* msg, const std::string& rid, const std::map<std::string, std::string>* attrs,
+                          bool* spent = nullptr) {
+    (void)src_meta_pb, (void)path, (void)key_src, (void)key_dst, (void)nonce, (void)etag_md5, (void)msg, (void)rid,
+        (void)attrs;
+    if (spent) *spent = false;
+    return FastClient::NotHandled;
+  }
   // calls a first-choice path declined and a second one served (LocalFirstFrontStore)
   virtual uint64_t fallbacks() const { return 0; }
 };
@@ -146,6 +158,11 @@ class FastFrontStore final : public FrontStore {
                         const std::string& etag_md5, int* replicas, std::string* msg, Times* t, const std::string& rid,
                         const std::map<std::string, std::string>* attrs, bool* spent = nullptr) override {
     return fc_->sse_write_slot(path, slot, n, key, nonce, etag_md5, replicas, msg, t, rid, attrs, spent);
+  }
+  Status sse_copy(const std::string& src_meta_pb, const std::string& path, const uint8_t key_src[32],
+                  const uint8_t key_dst[32], const uint8_t nonce[12], const std::string& etag_md5, std::string* msg,
+                  const std::string& rid, const std::map<std::string, std::string>* attrs, bool* spent = nullptr) override {
+    return fc_->sse_copy(src_meta_pb, path, key_src, key_dst, nonce, etag_md5, msg, rid, attrs, spent);
   }
 
  private:
@@ -232,6 +249,11 @@ class LocalFirstFrontStore final : public FrontStore {
                         const std::string& etag_md5, int* replicas, std::string* msg, Times* t, const std::string& rid,
                         const std::map<std::string, std::string>* attrs, bool* spent = nullptr) override {
     return fc_->sse_write_slot(path, slot, n, key, nonce, etag_md5, replicas, msg, t, rid, attrs, spent);
+  }
+  Status sse_copy(const std::string& src_meta_pb, const std::string& path, const uint8_t key_src[32],
+                  const uint8_t key_dst[32], const uint8_t nonce[12], const std::string& etag_md5, std::string* msg,
+                  const std::string& rid, const std::map<std::string, std::string>* attrs, bool* spent = nullptr) override {
+    return fc_->sse_copy(src_meta_pb, path, key_src, key_dst, nonce, etag_md5, msg, rid, attrs, spent);
   }
   Status list_components(const std::string& prefix, std::set<std::string>* out, const std::string& rid) override {
     if (fc_->list_components(prefix, out, rid) == FastClient::Ok) return FastClient::Ok;

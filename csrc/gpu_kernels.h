@@ -26,6 +26,9 @@
 //   K7 write  sse_write_kernel: a PUT of an SSE-S3 object in one pass over the gateway's slot — the
 //          plaintext loaded over PCIe, encrypted and authenticated in registers, the slices
 //          checksummed on the matrix cores, and the blob stored to its HBM extent and back in place.
+//   K7 copy  sse_rekey_kernel: a CopyObject of an SSE-S3 object in one pass from one HBM extent to
+//          another — the source's slices verified and its ciphertext authenticated, both keystreams
+//          XORed into it in registers, the new ciphertext authenticated, checksummed and stored.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -380,6 +383,59 @@ uint64_t sse_write_fused_min_bytes();
 void set_sse_write_fused(bool on, int64_t min_bytes = -1);
 void reset_sse_write_fused();
 hipError_t launch_sse_write(const SseWriteLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// K7 copy (sse_rekey_kernel): a CopyObject of an SSE-S3 object in one pass, HBM to HBM. `src` is a
+// stored blob [nonce 12][ciphertext n][tag 16], n >= 1, resident at a 16 B aligned extent readable up
+// to the next 16 B boundary behind its end, with its .meta image `src_meta`; `dst` another 16 B
+// aligned extent padded to 16 B, disjoint from the first, and `meta` its .meta image. The kernel
+// verifies every slice of the source against src_meta (`part_bad`: the per-workgroup minimum bad
+// slice, 0xFFFFFFFF none), absorbs the old ciphertext under `from`, XORs the keystream of `from`
+// with the nonce it reads from the blob and that of `to` with `nonce` into it, absorbs the new
+// ciphertext under `to`, and stores [nonce][new ciphertext][zeros] to dst. It leaves what
+// sse_read_kernel leaves for the source (from.part, part_bad, nonce_tag: gcm::tag_matches closes it)
+// and what sse_write_kernel leaves for the destination (to.part, meta, meta_host, part_crc: the host
+// closes the tag, writes it and checksums its slices). Both sides share the plan
+// gcm::plan_for(kSseReadTileBytes * ntiles), ntiles = sse_read_tiles(n), whose grid is the launch's;
+// `from` is gcm::prepare_keyed's and `to` gcm::prepare's for it, and either hjump is gcm::write_jump:
+// a chunk absorbs five elements on both sides. The host must look at part_bad and the source's tag
+// before anything names the destination's bytes. part, part_bad, part_crc, nonce_tag and meta_host
+// are device-visible host words.
+struct SseRekeySide {
+  uint32_t rk[60];
+  gcm::U128 h, hjump, tree[gcm::kGcmTreeSteps];
+  gcm::U128* part;  // [grid]
+};
+struct SseRekeyLaunch {
+  const uint8_t* src;
+  const uint32_t* src_meta;
+  uint8_t* dst;
+  uint32_t* meta;
+  uint32_t* meta_host;
+  uint64_t n, ntiles;
+  uint32_t full_init, tail_init;  // S(512), S((n + 28) % 512)
+  uint32_t nonce[3];              // the destination's
+  SseRekeySide from, to;
+  uint32_t* part_bad;  // [grid]
+  uint32_t* part_crc;  // [grid]
+  uint8_t* nonce_tag;  // [28]: the source's
+  // [kSseRekeyTailBytes]: the new blob from slice sse_write_body_slices(n) on, as whole 16 B vectors
+  // (under 528 bytes of ciphertext and zeros), for the host's checksum of the slices that hold the tag
+  uint8_t* tail_host;
+};
+constexpr uint64_t kSseRekeyTailBytes = 544;
+// DFS_SSE_COPY_FUSED=0 keeps the staged route (sse_read into a temporary, sse_crypt under the new key,
+// write), and blobs whose plaintext is below sse_copy_fused_min_bytes() stay on it.
+// DFS_SSE_COPY_FUSED_MIN_BYTES overrides the floor; set_sse_copy_fused is the benches' and tests'
+// switch (min_bytes < 0 keeps it). Measured (profiles/r14), a call costs ~300 us before the first byte
+// (two key preparations, launch, synchronise, two GHASH trees, H_dst^-vback), which the staged route
+// undercuts at 64 KiB (139 us); 1 MiB is the smallest measured size the kernel wins, on hbm-ack
+// (322 against 569 us) and nvme-sync stores (443 against 598 us) alike, so nothing gates it by durability.
+// That rests on one run of three repetitions per route, with no size between 64 KiB and 1 MiB taken.
+constexpr uint64_t kSseCopyFusedMinBytes = 1ull << 20;
+bool sse_copy_fused_enabled();
+uint64_t sse_copy_fused_min_bytes();
+void set_sse_copy_fused(bool on, int64_t min_bytes = -1);
+hipError_t launch_sse_rekey(const SseRekeyLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

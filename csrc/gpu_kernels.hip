@@ -2547,6 +2547,248 @@ __global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2
   if (threadIdx.x == 0) a.part_crc[blockIdx.x] = wacc[0] ^ wacc[1] ^ wacc[2] ^ wacc[3];
 }
 
+// ---- K7 copy: verify, authenticate, re-key, authenticate, checksum and land a CopyObject in one pass ----
+//
+// Source and destination blobs are both [nonce 12][ciphertext n][tag 16] in HBM extents, 16 B aligned,
+// so ciphertext byte i sits at blob byte 12 + i on either side and the new ciphertext is
+// old ^ keystream(K_src, nonce_src) ^ keystream(K_dst, nonce_dst) at the same offset: vector v is
+// loaded from src + 16v and stored to dst + 16v. The plaintext exists between two XORs, in registers.
+//
+// Which axis the AES runs on: sse_write_kernel's. A lane keeps its own 64 B chunk of the CRC axis
+// (tile T is blob bytes [16 KiB * T, 16 KiB * (T + 1)), thread t owns vectors g = 1024 T + 4t .. g + 3)
+// and computes, per key, the keystream of the five AES blocks g - 1 .. g + 3 that the chunk touches.
+// sse_read_kernel's 3-dword funnel would save two of the ten blocks, but here the bytes must come
+// back to the CRC axis for the second checksum and the aligned store, so it would take a funnel in
+// (16 shuffles and lane 63's extra load) and a funnel out (3 more shuffles, and the wave's first three
+// dwords stored by the wave below): lane exchanges both ways and stores that are no longer whole
+// vectors, against two AES blocks that ride in the rounds of the other four. With the chunk kept
+// where it is, the first CRC reads the loaded registers, the second the re-keyed ones, and no lane
+// reads another's bytes.
+//   GHASH, twice. The old ciphertext is absorbed under H_src and the new one under H_dst, each as
+// sse_write_kernel does: the tail of block g - 1, blocks g .. g + 2, the head of block g + 3, five
+// elements per chunk by linearity, a lane's step between its tiles gcm::write_jump for that key. The
+// nonce dwords and every byte from 12 + n on count as zero on both sides, so the source's partials
+// fold to what sse_read_kernel's would (gcm::tag_matches on the host) and the destination's to what
+// sse_write_kernel's would (gcm::unfold, gcm::finish_tag). The source's nonce is read from its first
+// three dwords; the host learns it, and the stored tag, from `nonce_tag`.
+//
+// CRC, twice, on the matrix cores through the permlane32 route. The loaded chunk is compared with the
+// source's .meta image (minimum bad slice per workgroup; the short tail slice by workgroup 0 from
+// byte loads, as sse_read_kernel). The re-keyed chunk gives the .meta words of the slices in front
+// of the tag, to HBM and to the host image, and the raw whole-block partials, as sse_write_kernel.
+// The slices behind them hold the tag, which only the host can close: their bytes (under 528, with
+// zeros for the tag) are stored a second time into `tail_host`, so the host checksums them without a
+// copy back; they are all of the payload that crosses the link.
+//   The kernel stores before it can know that the source verifies: the host looks at part_bad and
+// the source's tag first, and releases the extent unless both hold, so no block ever names those
+// bytes.
+//
+// Scalar registers. Two key schedules are 120 words, and two sets of H, jump and tree powers 72 more:
+// they do not fit the scalar file. All of it stays in the kernel-argument segment. The AES round
+// loop is not unrolled and indexes the schedule by the round, so the compiler loads the four words
+// of a round from the segment as the round begins (one scalar load of four dwords, for either key),
+// and H, the jump and the tree steps are loaded where they are used; only one schedule's round and
+// one power of H are live at a time. The two keystreams run one after the other over the same 20
+// state registers. Two waves per SIMD as the read and write kernels (the CRC basis alone is 64
+// registers), no scratch: see the resource report in profiles/r14.
+__device__ __forceinline__ WaveData chunk_operand(const uint32_t (&c)[16]) {
+  uint32_t p0[8], p1[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const auto r = __builtin_amdgcn_permlane32_swap(c[k], c[8 + k], false, false);
+    p0[k] = r[0];  // lanes 0..31: own dword k; lanes 32..63: dword 8 + k of lane - 32
+    p1[k] = r[1];  // lanes 0..31: dword k of lane + 32; lanes 32..63: own dword 8 + k
+  }
+  WaveData w;
+  w.v[0] = make_uint4(p0[0], p0[1], p0[2], p0[3]);
+  w.v[1] = make_uint4(p0[4], p0[5], p0[6], p0[7]);
+  w.v[2] = make_uint4(p1[0], p1[1], p1[2], p1[3]);
+  w.v[3] = make_uint4(p1[4], p1[5], p1[6], p1[7]);
+  return w;
+}
+
+// The five elements of a chunk on the CRC axis (its dwords c, zero where no ciphertext stands).
+__device__ __forceinline__ gcm::U128 ghash_absorb_chunk(gcm::U128 acc, const gcm::U128& h, const uint32_t (&c)[16]) {
+  const uint32_t e0[4] = {0, c[0], c[1], c[2]};
+  acc = ghash_absorb(acc, h, e0);
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const uint32_t e[4] = {c[4 * b + 3], c[4 * b + 4], c[4 * b + 5], c[4 * b + 6]};
+    acc = ghash_absorb(acc, h, e);
+  }
+  const uint32_t e4[4] = {c[15], 0, 0, 0};
+  return ghash_absorb(acc, h, e4);
+}
+
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void sse_rekey_kernel(
+    SseRekeyLaunch a, const DevCrcTables* __restrict__ gt) {
+  static_assert(kCrcWgThreads == 256 && gcm::kGcmTileBlocks * 16 == kSlicesPerTile * 512, "a CRC tile is a GCM tile");
+  __shared__ MfmaTileLds lt;
+  __shared__ uint32_t te0[256];
+  __shared__ uint8_t sbox[256];
+  __shared__ gcm::U128 wave_part_src[4], wave_part_dst[4];
+  __shared__ uint32_t wacc[4];
+  __shared__ uint32_t wg_bad;
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sw = lane >> 3, sl = lane & 7;
+  const int64_t n = static_cast<int64_t>(a.n), size = n + 28, nvec = (size + 15) / 16, s_full = size / 512;
+  const int64_t s_body = static_cast<int64_t>(sse_write_body_slices(a.n));
+  const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(a.src);
+  auto first_vector = [&](uint64_t tile) { return static_cast<int64_t>(tile * gcm::kGcmTileBlocks + 4 * threadIdx.x); };
+  auto fetch = [&](uint64_t tile, uint4 (&v)[4]) {
+    const int64_t g = first_vector(tile);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[i] = make_uint4(0, 0, 0, 0);
+      if (g + i < nvec) {  // the vector behind the block's end is never loaded
+        const u32x4 x = __builtin_nontemporal_load(src + g + i);
+        v[i] = make_uint4(x[0], x[1], x[2], x[3]);
+      }
+    }
+  };
+
+  // Zero where no ciphertext stands: the nonce's dwords in the blob's first chunk, and every byte from
+  // 12 + n on. Only those few chunks take the branch, so no mask is live through the AES rounds.
+  auto mask = [&](int64_t g, uint32_t (&c)[16]) {
+    if (g != 0 && 16 * g + 64 <= 12 + n) return;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int64_t p = 16 * g + 4 * i;  // the dword's first byte in the blob
+      c[i] = p < 12 ? 0u : c[i] & sse_keep(12 + n - p);
+    }
+  };
+
+  uint4 cur[4];
+  fetch(blockIdx.x, cur);
+  i32x4 A[16];
+  load_basis(reinterpret_cast<const i32x4*>(gt + 1), lane, A);
+  load_lds_image(gt, &lt);
+  sse_load_tables(gt, te0, sbox);
+  if (threadIdx.x == 0) wg_bad = 0xFFFFFFFFu;
+  // the source's nonce: the block's first three dwords, the same for every lane
+  const uint32_t* head = reinterpret_cast<const uint32_t*>(a.src);
+  const uint32_t s0 = head[0], s1 = head[1], s2 = head[2];
+  if (blockIdx.x == 0 && threadIdx.x < 28)  // nonce and stored tag for the host: block bytes [0, 12) and [12 + n, 28 + n)
+    a.nonce_tag[threadIdx.x] = a.src[threadIdx.x < 12 ? threadIdx.x : n + threadIdx.x];
+  __syncthreads();
+
+  gcm::U128 acc_src{0, 0}, acc_dst{0, 0};
+  uint32_t bad = 0xFFFFFFFFu, crc = 0;
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    uint4 nxt[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+    if (tile + gridDim.x < a.ntiles) fetch(tile + gridDim.x, nxt);
+    const int64_t g = first_vector(tile);
+    const int64_t slice = static_cast<int64_t>(tile) * kSlicesPerTile + wave * 8 + sw;
+    uint32_t c[16] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                      cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+
+    // verify the source: the chunk as loaded
+    {
+      const uint32_t r = slice_from_chunks(lt, wave_chunk_crcs(A, chunk_operand(c), lane), lane);
+      if (slice < s_full && sl == 0 && a.src_meta[slice] != __builtin_bswap32(r ^ a.full_init))
+        bad = min(bad, static_cast<uint32_t>(slice));
+    }
+
+    // authenticate the source: its ciphertext alone, zero where the nonce, the tag and the rest stand
+    mask(g, c);
+    if (tile != blockIdx.x) acc_src = gcm::gf128_mul(a.from.hjump, acc_src);
+    acc_src = ghash_absorb_chunk(acc_src, a.from.h, c);
+
+    // re-key: the keystreams of blocks g - 1 .. g + 3 under either key, one after the other; chunk
+    // dword i takes dword (i + 1) % 4 of block g - 1 + (i + 1) / 4
+    {
+      uint32_t ks[5][4];
+#pragma unroll
+      for (int b = 0; b < 5; ++b) {
+        ks[b][0] = s0;
+        ks[b][1] = s1;
+        ks[b][2] = s2;
+        ks[b][3] = gcm::bswap32(1u + static_cast<uint32_t>(g + b));
+      }
+      gcm::aes256_encrypt_words<5>(te0, sbox, a.from.rk, ks);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) c[i] ^= ks[(i + 1) >> 2][(i + 1) & 3];
+#pragma unroll
+      for (int b = 0; b < 5; ++b) {
+        ks[b][0] = a.nonce[0];
+        ks[b][1] = a.nonce[1];
+        ks[b][2] = a.nonce[2];
+        ks[b][3] = gcm::bswap32(1u + static_cast<uint32_t>(g + b));
+      }
+      gcm::aes256_encrypt_words<5>(te0, sbox, a.to.rk, ks);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) c[i] ^= ks[(i + 1) >> 2][(i + 1) & 3];
+    }
+    mask(g, c);
+
+    // authenticate the destination, then put its nonce where it belongs: no part of any element
+    if (tile != blockIdx.x) acc_dst = gcm::gf128_mul(a.to.hjump, acc_dst);
+    acc_dst = ghash_absorb_chunk(acc_dst, a.to.h, c);
+    if (g == 0) {
+      c[0] = a.nonce[0];
+      c[1] = a.nonce[1];
+      c[2] = a.nonce[2];
+    }
+
+    // land: the extent is padded to 16 B; zeros where the tag goes and behind it
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t pos = 16 * (g + i);
+      if (pos >= size) continue;
+      const uint4 v = make_uint4(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+      *reinterpret_cast<uint4*>(a.dst + pos) = v;
+      // the host's slices (at most 512 + 15 bytes and the pad) also where it can checksum them
+      if (pos >= s_body * 512) *reinterpret_cast<uint4*>(a.tail_host + (pos - s_body * 512)) = v;
+    }
+
+    // checksum the destination: the slices in front of the tag, and the whole-block partial
+    {
+      uint32_t r = slice_from_chunks(lt, wave_chunk_crcs(A, chunk_operand(c), lane), lane);
+      if (slice >= s_body) {
+        r = 0;  // the host's slices, and zeros to the whole-block CRC
+      } else if (sl == 0) {
+        const uint32_t be = __builtin_bswap32(r ^ a.full_init);
+        a.meta[slice] = be;
+        a.meta_host[slice] = be;
+      }
+      r = combine<8>(r, lane, lt.sh512);
+      r = combine<16>(r, lane, lt.sh1k);
+      r = combine<32>(r, lane, lt.sh2k);  // wave-uniform: the 4 KiB sub-tile's raw CRC
+      if (tile != blockIdx.x) {
+        uint32_t e = gridDim.x;
+        for (int b = 0; e; ++b, e >>= 1)
+          if (e & 1) crc = mat_apply(lt.tile_pow2[b], crc, lane);
+      }
+      crc ^= r;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+  }
+
+  if (size % 512 && blockIdx.x == 0 && wave == 0) {  // the source's short tail slice
+    const uint32_t tail_len = static_cast<uint32_t>(size % 512);
+    const uint32_t r =
+        slice_from_chunks(lt, wave_chunk_crcs(A, load_tail_wave(a.src + s_full * 512, tail_len, lane), lane), lane);
+    if (lane == 0 && a.src_meta[s_full] != __builtin_bswap32(r ^ a.tail_init)) bad = min(bad, static_cast<uint32_t>(s_full));
+  }
+  if (bad != 0xFFFFFFFFu) atomicMin(&wg_bad, bad);
+  // the wave's CRC stands at the end of its sub-tile in the workgroup's last tile: to the axis's end
+  {
+    for (int k = wave; k < 3; ++k) crc = tab4(lt.sh4k, crc);
+    const uint64_t last = blockIdx.x + (a.ntiles - 1 - blockIdx.x) / gridDim.x * gridDim.x;
+    uint64_t e = a.ntiles - 1 - last;
+    for (int b = 0; e; ++b, e >>= 1)
+      if (e & 1) crc = mat_apply(lt.tile_pow2[b], crc, lane);
+    if (lane == 0) wacc[wave] = crc;
+  }
+  ghash_wg_partial(acc_src, a.from.tree, wave_part_src, a.from.part);  // its barrier orders wg_bad and wacc too
+  ghash_wg_partial(acc_dst, a.to.tree, wave_part_dst, a.to.part);
+  if (threadIdx.x == 0) {
+    a.part_bad[blockIdx.x] = wg_bad;
+    a.part_crc[blockIdx.x] = wacc[0] ^ wacc[1] ^ wacc[2] ^ wacc[3];
+  }
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -3147,6 +3389,47 @@ hipError_t launch_sse_write(const SseWriteLaunch& a, const DevCrcTables* t, int 
       reinterpret_cast<uintptr_t>(a.part) % 16 || a.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(sse_write_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_sse_copy_fused{-1};
+// -1 = DFS_SSE_COPY_FUSED_MIN_BYTES, else kSseCopyFusedMinBytes
+static std::atomic<int64_t> g_sse_copy_min_bytes{-1};
+
+void set_sse_copy_fused(bool on, int64_t min_bytes) {
+  g_sse_copy_fused.store(on ? 1 : 0);
+  if (min_bytes >= 0) g_sse_copy_min_bytes.store(min_bytes);
+}
+
+uint64_t sse_copy_fused_min_bytes() {
+  int64_t v = g_sse_copy_min_bytes.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_COPY_FUSED_MIN_BYTES");
+    g_sse_copy_min_bytes.store(v = e && std::atoll(e) >= 0 ? std::atoll(e) : static_cast<int64_t>(kSseCopyFusedMinBytes));
+  }
+  return static_cast<uint64_t>(v);
+}
+
+bool sse_copy_fused_enabled() {
+  int v = g_sse_copy_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_COPY_FUSED");
+    g_sse_copy_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+hipError_t launch_sse_rekey(const SseRekeyLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const gcm::Plan p = gcm::plan_for(kSseReadTileBytes * sse_read_tiles(a.n));
+  const uintptr_t src = reinterpret_cast<uintptr_t>(a.src), dst = reinterpret_cast<uintptr_t>(a.dst);
+  const uint64_t span = (a.n + 28 + 15) / 16 * 16;
+  if (!t || !a.src || !a.src_meta || !a.dst || !a.meta || !a.meta_host || !a.from.part || !a.to.part || !a.part_bad ||
+      !a.part_crc || !a.nonce_tag || !a.tail_host || reinterpret_cast<uintptr_t>(a.tail_host) % 16 || a.n == 0 || p.nblocks > 0xFFFFFFFEull || src % 16 || dst % 16 ||
+      reinterpret_cast<uintptr_t>(a.from.part) % 16 || reinterpret_cast<uintptr_t>(a.to.part) % 16 ||
+      a.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
+    return hipErrorInvalidValue;
+  if (src < dst + span && dst < src + span) return hipErrorInvalidValue;  // two extents, never one in place
+  hipLaunchKernelGGL(sse_rekey_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
   return hipGetLastError();
 }
 

@@ -2934,6 +2934,33 @@ bool S3Front::native_copy(Conn* c, Req& r, const std::string& dest) {
   std::map<std::string, std::string> src_attrs;
   uint64_t n = 0;
   bool at12 = false;  // the plaintext sits after a 12-byte nonce (a decrypted SSE source)
+  // the destination's attributes: the ETag, and the source's (COPY) or the request's (REPLACE) metadata
+  auto dest_attrs = [&](const std::string& etag) {
+    std::map<std::string, std::string> attrs{{"ETag", etag}};
+    const std::string* dir = r.get("x-amz-metadata-directive");
+    std::string directive = dir ? *dir : "COPY";
+    for (auto& ch : directive) ch = static_cast<char>(std::toupper(static_cast<unsigned char>(ch)));
+    if (directive == "REPLACE") {
+      for (auto& h : r.headers)
+        if (h.first.compare(0, 11, "x-amz-meta-") == 0) attrs[h.first] = h.second;
+    } else {
+      for (auto& kv : src_attrs)
+        if (kv.first.compare(0, 11, "x-amz-meta-") == 0 || kv.first == "Content-Type") attrs[kv.first] = kv.second;
+    }
+    return attrs;
+  };
+  auto answer = [&](const std::map<std::string, std::string>& attrs, const std::string& etag, uint64_t bytes) {
+    (void)write_sidecar(dest, attrs, r.rid);
+    {
+      std::lock_guard<std::mutex> g(st_mu_);
+      st_.copies++;
+      st_.copy_bytes += bytes;
+    }
+    int64_t ms;
+    return respond(c, r, 200,
+                   "<CopyObjectResult>" + xel("LastModified", iso_now(now_s(), &ms)) + xel("ETag", etag) +
+                       "</CopyObjectResult>");
+  };
   if (found) {
     pb::FileMetadata m;
     if (!m.decode(meta)) return proxy(c, r, nullptr, 0, "copy-attrs");
@@ -2942,6 +2969,49 @@ bool S3Front::native_copy(Conn* c, Req& r, const std::string& dest) {
     auto dk = src_attrs.find("x-amz-sse-encrypted-dek");
     const bool enc = dk != src_attrs.end();
     if (enc && !sse) return proxy(c, r, nullptr, 0, "sse");
+    // Re-keyed where it is stored (FrontStore::sse_copy): no slot, no payload here, and no MD5, for a
+    // plain SSE object's ETag attribute already is the MD5 of its plaintext. Anything but Ok, or a
+    // failure after the op was sent, leaves the route below as it always ran.
+    auto et = src_attrs.find("ETag");
+    if (sse_offload() && sse && enc && src != dest && m.size > 28 && et != src_attrs.end() && et->second.size() == 34 &&
+        et->second.front() == '"' && et->second.back() == '"' &&
+        et->second.find_first_not_of("0123456789abcdef", 1) == 33) {
+      std::string wrapped, key;
+      bool unwrapped = crypto::base64_decode(dk->second, &wrapped) && wrapped.size() >= 60;
+      if (unwrapped) {
+        try {
+          key = crypto::aes256gcm_decrypt(cfg_.sse_kek, wrapped.substr(0, 12), wrapped.substr(12), "");
+        } catch (const std::exception&) {
+          unwrapped = false;
+        }
+      }
+      if (unwrapped && key.size() == 32) {
+        const std::string etag = et->second, md5 = etag.substr(1, 32);
+        std::map<std::string, std::string> attrs = dest_attrs(etag);
+        const std::string ndk = crypto::random_bytes(32), n1 = crypto::random_bytes(12), n2 = crypto::random_bytes(12);
+        attrs["x-amz-sse-encrypted-dek"] = crypto::base64_encode(n2 + crypto::aes256gcm_encrypt(cfg_.sse_kek, n2, ndk, ""));
+        bool spent = false;
+        auto copy = [&] {
+          return fc_->sse_copy(meta, dest, reinterpret_cast<const uint8_t*>(key.data()),
+                               reinterpret_cast<const uint8_t*>(ndk.data()), reinterpret_cast<const uint8_t*>(n1.data()),
+                               md5, &msg, r.rid, &attrs, &spent);
+        };
+        auto st14 = copy();
+        if (st14 == FastClient::Failed && !spent && msg.find("already exists") != std::string::npos) {
+          std::string dmsg;
+          if (fc_->remove(dest, &dmsg, r.rid) != FastClient::NotHandled) st14 = copy();
+        }
+        if (st14 == FastClient::Ok) {
+          {
+            std::lock_guard<std::mutex> g(st_mu_);
+            st_.sse_offloaded++;
+          }
+          return answer(attrs, etag, m.size - 28);
+        }
+        if (st14 == FastClient::Failed && spent) return proxy(c, r, nullptr, 0, "copy-fallback");  // the copy again, in Python
+        msg.clear();
+      }
+    }
     if (m.size + (enc ? 0 : room) > fc_->slot_bytes()) return proxy(c, r, nullptr, 0, "large");
     if (m.size > 0) {
       uint64_t got = 0;
@@ -3014,17 +3084,7 @@ bool S3Front::native_copy(Conn* c, Req& r, const std::string& dest) {
   uint8_t* b = fc_->slot_mut(slot);
   const std::string md5 = crypto::md5_hex(at12 ? b + 12 : b, n);
   const std::string etag = "\"" + md5 + "\"";
-  std::map<std::string, std::string> attrs{{"ETag", etag}};
-  const std::string* dir = r.get("x-amz-metadata-directive");
-  std::string directive = dir ? *dir : "COPY";
-  for (auto& ch : directive) ch = static_cast<char>(std::toupper(static_cast<unsigned char>(ch)));
-  if (directive == "REPLACE") {
-    for (auto& h : r.headers)
-      if (h.first.compare(0, 11, "x-amz-meta-") == 0) attrs[h.first] = h.second;
-  } else {
-    for (auto& kv : src_attrs)
-      if (kv.first.compare(0, 11, "x-amz-meta-") == 0 || kv.first == "Content-Type") attrs[kv.first] = kv.second;
-  }
+  std::map<std::string, std::string> attrs = dest_attrs(etag);
   uint64_t stored = n;
   if (sse) {  // SseManager.encrypt_object: a fresh DEK, wrapped by the KEK
     if (!at12) std::memmove(b + 12, b, n);
@@ -3044,16 +3104,7 @@ bool S3Front::native_copy(Conn* c, Req& r, const std::string& dest) {
       st = fc_->write_slot(dest, slot, stored, &reps, &msg, &t, r.rid, &attrs, nullptr, &md5w);
   }
   if (st != FastClient::Ok) return proxy(c, r, nullptr, 0, "copy-fallback");  // the copy again, in Python
-  (void)write_sidecar(dest, attrs, r.rid);
-  {
-    std::lock_guard<std::mutex> g(st_mu_);
-    st_.copies++;
-    st_.copy_bytes += n;
-  }
-  int64_t ms;
-  return respond(c, r, 200,
-                 "<CopyObjectResult>" + xel("LastModified", iso_now(now_s(), &ms)) + xel("ETag", etag) +
-                     "</CopyObjectResult>");
+  return answer(attrs, etag, n);
 }
 
 // ---------------------------------------------------------------- a front without Python

@@ -148,6 +148,21 @@ class FastPathClient:
         st, _total, replicas, msg = self._call(13, body)
         return st, replicas if st == OK else 0, int(msg, 16) if st == OK else 0
 
+    def sse_copy(self, src_id: str, dst_id: str, key_src: bytes, key_dst: bytes, nonce: bytes, term: int,
+                 next_servers: list[str] | tuple = (), shm_path: str = "", request_id: str | None = None):
+        """CopyObject of an SSE-S3 object by one kernel on the chunkserver's GPU (csrc/fastpath.cpp op 14):
+        the stored blob ``src_id`` is verified, authenticated and re-keyed under (``key_dst``, ``nonce``)
+        into the new block ``dst_id``, HBM to HBM, with no slot, and fanned out to ``next_servers`` from HBM
+        over their P2P pairs. Returns (status, replicas_written, crc of the new blob): OK, NOT_FOUND,
+        CORRUPT, AUTH_FAILED, FENCED, IO_ERROR, or UNSUPPORTED, with nothing done, when the kernel would
+        not take it or a server of ``next_servers`` has no device P2P pair up."""
+        body = struct.pack("<Q", term) + _s(src_id.encode()) + _s(dst_id.encode()) + _s(shm_path.encode())
+        body += _s(key_src) + _s(key_dst) + _s(nonce)
+        body += struct.pack("<H", len(next_servers)) + b"".join(_s(a.encode()) for a in next_servers)
+        body += _s(self._rid(request_id))
+        st, _total, replicas, msg = self._call(14, body)
+        return st, replicas if st == OK else 0, int(msg, 16) if st == OK else 0
+
     @staticmethod
     def _rid(request_id: str | None) -> bytes:
         from .rpc import current_request_id

@@ -766,6 +766,117 @@ static int ec_read_bench(int device, const std::string& dir, int reps) {
   return rc;
 }
 
+// --sse-ec-read: a GET of an SSE-S3 object held as a resident RS(6,3) file, with 0 and 1 lost data
+// column, into a registered buffer: [1] ChunkStore::sse_ec_read's one-kernel route against [0] what a
+// GET costs without it (ec_read_range of the whole blob into the slot, then sse_crypt where the
+// ciphertext lies, under sse_crypt's own floor), alternating in every repetition. One JSON line per
+// (size, lost); times are microseconds per call, each the mean of `iters` back-to-back calls, with the
+// median and the spread (max - min over the repetitions) of either route. `n` counts plaintext bytes.
+static int sse_ec_read_bench(int device, const std::string& dir, int reps) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    std::fprintf(stderr, "--sse-ec-read needs a GPU\n");
+    return 1;
+  }
+  std::filesystem::remove_all(dir);
+  StoreConfig cfg;
+  cfg.storage_dir = dir + "/sse_ec_read";
+  cfg.device = device;
+  cfg.hbm_capacity = 1ull << 30;
+  ChunkStore s(cfg);
+  uint8_t key[32], nonce[12];
+  for (int i = 0; i < 32; ++i) key[i] = static_cast<uint8_t>(3 * i + 1);
+  for (int i = 0; i < 12; ++i) nonce[i] = static_cast<uint8_t>(7 * i + 5);
+  const int k = 6, m = 3;
+  int rc = 0;
+  for (uint64_t n : {64ull << 10, 1ull << 20, 4ull << 20, 100ull << 20}) {
+    const auto plain = random_bytes(n, static_cast<uint32_t>(n + 37));
+    const uint64_t orig = n + 28, len = (orig + k - 1) / k;
+    std::vector<uint8_t> blob(k * len, 0);
+    std::memcpy(blob.data(), nonce, 12);
+    std::memcpy(blob.data() + 12, plain.data(), n);
+    crypto::aes256gcm_encrypt_inplace(key, nonce, blob.data() + 12, n, blob.data() + 12 + n);
+    std::vector<std::vector<uint8_t>> par(m, std::vector<uint8_t>(len));
+    std::vector<const uint8_t*> in(k);
+    std::vector<uint8_t*> outp(m);
+    for (int c = 0; c < k; ++c) in[c] = blob.data() + c * len;
+    for (int r = 0; r < m; ++r) outp[r] = par[r].data();
+    gf::Matrix full = gf::rs_matrix(k, m), parity(full.begin() + k, full.end());
+    gf::matmul_cpu(parity, in.data(), outp.data(), len);
+    std::vector<std::string> ids;
+    std::vector<const uint8_t*> dev(k + m, nullptr);
+    bool ok = true;
+    for (int i = 0; i < k + m; ++i) {
+      const uint8_t* p = i < k ? in[i] : par[i - k].data();
+      ids.push_back("secr_" + std::to_string(n) + "_" + std::to_string(i));
+      ok = ok && s.write(ids[i], p, len, crc32(p, len)).ok;
+      uint64_t size = 0;
+      if (ok) dev[i] = s.pin_device(ids[i], &size);
+      ok = ok && dev[i] && size == len;
+    }
+    uint8_t* out = nullptr;
+    if (!ok || hipHostMalloc(reinterpret_cast<void**>(&out), orig + 64, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
+      return 1;
+    s.register_host(out, orig + 64);
+    const int iters = static_cast<int>(std::clamp<uint64_t>((64ull << 20) / n, 2, 100));
+    for (int lost = 0; lost <= 1; ++lost) {
+      std::vector<const uint8_t*> shards = dev;
+      if (lost) shards[1] = nullptr;
+      std::vector<double> us[2];  // [0] ec_read_range + sse_crypt, [1] the kernel
+      bool match = true;
+      auto run = [&](int fused, int count) {
+        std::memset(out, 0, orig);
+        const auto t0 = Clock::now();
+        for (int i = 0; i < count && match; ++i) {
+          std::string err;
+          if (fused) {
+            uint64_t got = 0;
+            match = s.sse_ec_read(shards, k, m, len, orig, key, out, n, &got, &err, true) == ChunkStore::SseRead::Ok && got == n;
+          } else {
+            match = s.ec_read_range(shards, k, m, len, 0, orig, out, &err) == ChunkStore::EcRead::Ok &&
+                    s.sse_crypt(out + 12, n, key, out, false, out + 12 + n, &err);
+          }
+        }
+        const double t = secs(t0, Clock::now()) * 1e6 / count;
+        match = match && std::memcmp(out + (fused ? 0 : 12), plain.data(), n) == 0;
+        return t;
+      };
+      set_sse_ec_read_fused(true, 0);  // every size takes the kernel: the floor is what this measures
+      for (int fused = 0; fused < 2; ++fused) run(fused, 2);  // warm-up: code objects, scratch
+      const uint64_t before = s.stats().sse_fused_ec_reads;
+      for (int rep = 0; rep < reps; ++rep)
+        for (int fused = 1; fused >= 0; --fused) us[fused].push_back(run(fused, iters));
+      match = match && s.stats().sse_fused_ec_reads - before == static_cast<uint64_t>(reps) * iters;
+      auto list = [](const std::vector<double>& v) {
+        std::string o;
+        for (double x : v) o += (o.empty() ? "" : ", ") + std::to_string(x);
+        return o;
+      };
+      auto median = [](std::vector<double> v) {
+        std::sort(v.begin(), v.end());
+        return v[v.size() / 2];
+      };
+      auto spread = [](const std::vector<double>& v) { return *std::max_element(v.begin(), v.end()) - *std::min_element(v.begin(), v.end()); };
+      std::printf("{\"sse_ec_read\": {\"k\": %d, \"m\": %d, \"n\": %llu, \"shard_len\": %llu, \"lost\": %d, \"iters\": %d, "
+                  "\"fused_us\": [%s], \"staged_us\": [%s], \"fused_median_us\": %.1f, \"staged_median_us\": %.1f, "
+                  "\"fused_spread_us\": %.1f, \"staged_spread_us\": %.1f, \"match\": %s}}\n",
+                  k, m, static_cast<unsigned long long>(n), static_cast<unsigned long long>(len), lost, iters,
+                  list(us[1]).c_str(), list(us[0]).c_str(), median(us[1]), median(us[0]), spread(us[1]), spread(us[0]),
+                  match ? "true" : "false");
+      std::fflush(stdout);
+      if (!match) rc = 1;
+    }
+    s.unregister_host(out);
+    (void)hipHostFree(out);
+    for (auto& id : ids) {
+      s.unpin(id);
+      s.remove(id);
+    }
+  }
+  std::filesystem::remove_all(dir);
+  return rc;
+}
+
 // --sse: ChunkStore::sse_crypt in place on a registered buffer whose body starts 12 bytes into a
 // 16 B vector (a slot's [nonce 12][body][tag 16]): the kernel path against OpenSSL on the calling
 // thread, alternating in every repetition, encrypt and decrypt. One JSON line per (size, direction)
@@ -1149,6 +1260,17 @@ int main(int argc, char** argv) {
         if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
       }
       return sse_bench(device, dir, std::max(5, reps));
+    }
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--sse-ec-read") {
+      std::string dir = "/tmp/io_bench_sse_ec_read";
+      int device = 0, reps = 5;
+      for (int j = 1; j + 1 < argc; ++j) {
+        if (std::string(argv[j]) == "--dir") dir = argv[j + 1];
+        if (std::string(argv[j]) == "--device") device = std::atoi(argv[j + 1]);
+        if (std::string(argv[j]) == "--reps") reps = std::atoi(argv[j + 1]);
+      }
+      return sse_ec_read_bench(device, dir, std::max(5, reps));
     }
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--ec-read") {

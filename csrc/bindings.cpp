@@ -266,6 +266,11 @@ PYBIND11_MODULE(_dfs_native, m) {
   // the shape of an sse_read_kernel launch: bytes of the blob per workgroup step, and the grid's cap
   m.attr("sse_read_tile_bytes") = kSseReadTileBytes;
   m.attr("sse_read_max_grid") = static_cast<int>(gcm::kGcmMaxGrid);
+  m.def("set_sse_ec_read_fused", &set_sse_ec_read_fused,
+        "GETs of SSE-S3 objects held as RS shards rebuilt, decrypted and delivered by one kernel (else ec_read_range, then sse_crypt)",
+        py::arg("on"), py::arg("min_bytes") = -1);
+  m.def("sse_ec_read_fused_min_bytes", &sse_ec_read_fused_min_bytes, "blobs with less plaintext than this stay staged");
+  m.attr("sse_ec_read_min_shard") = kSseEcReadMinShard;  // shorter shards stay staged
   m.def("set_ec_read_fused", &set_ec_read_fused, "degraded EC range reads in one kernel (else decode into HBM, then copies)");
   m.def("set_crc_wide", &set_crc_wide, "K1/K2 one workgroup per CU: 0 off, 1 shared LDS image, 2 + LDS basis");
   m.def("set_crc_kernels", [](bool mfma, int scrub_ring, int tile_ring) {
@@ -670,6 +675,44 @@ PYBIND11_MODULE(_dfs_native, m) {
         if (r != ChunkStore::EcRead::Ok) return py::none();
         return py::cast(want);
       }, py::arg("block_ids"), py::arg("k"), py::arg("m"), py::arg("shard_len"), py::arg("offset"), py::arg("length"),
+         py::arg("out"))
+      // GET of an SSE-S3 object held as an RS(k, m) file: the blob of `size` bytes is spelled by the
+      // resident blocks `block_ids` ("" = lost) of shard_len bytes; its plaintext goes into `out`. One
+      // kernel when `out` is registered and 16 B aligned. Returns (status, n, error): 0 Ok,
+      // 3 AuthFailed, 4 IoError.
+      .def("sse_ec_read", [](ChunkStore& s, std::vector<std::string> block_ids, int k, int m, uint64_t shard_len,
+                             uint64_t size, py::bytes key, py::buffer out) {
+        py::buffer_info bi = out.request(true);
+        std::string ky = key, err;
+        if (ky.size() != 32) throw std::invalid_argument("sse_ec_read: 32-byte key");
+        if (k <= 0 || m < 0 || block_ids.size() != static_cast<size_t>(k + m) || shard_len == 0)
+          throw std::invalid_argument("sse_ec_read: k + m block ids");
+        std::vector<const uint8_t*> shards(block_ids.size(), nullptr);
+        bool resident = true;
+        uint64_t n = 0;
+        ChunkStore::SseRead st = ChunkStore::SseRead::IoError;
+        {
+          py::gil_scoped_release rel;
+          for (size_t i = 0; i < block_ids.size() && resident; ++i) {
+            if (block_ids[i].empty()) continue;
+            uint64_t have = 0;
+            shards[i] = s.pin_device(block_ids[i], &have);
+            if (shards[i] && have != shard_len) {
+              s.unpin(block_ids[i]);
+              shards[i] = nullptr;
+            }
+            resident = shards[i] != nullptr;
+          }
+          if (resident)
+            st = s.sse_ec_read(shards, k, m, shard_len, size, reinterpret_cast<const uint8_t*>(ky.data()),
+                               static_cast<uint8_t*>(bi.ptr), static_cast<uint64_t>(bi.size * bi.itemsize), &n, &err);
+          for (size_t i = 0; i < block_ids.size(); ++i)
+            if (shards[i]) s.unpin(block_ids[i]);
+        }
+        gcm::wipe(&ky[0], ky.size());
+        if (!resident) throw std::runtime_error("sse_ec_read: a block is not resident at shard_len bytes");
+        return py::make_tuple(static_cast<int>(st), n, err);
+      }, py::arg("block_ids"), py::arg("k"), py::arg("m"), py::arg("shard_len"), py::arg("size"), py::arg("key"),
          py::arg("out"));
 
   // ---------------- native chunkserver control loop (csrc/cs_agent.cpp)

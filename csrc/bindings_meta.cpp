@@ -1138,6 +1138,27 @@ void bind_meta(py::module_& m) {
         return py::make_tuple(static_cast<int>(st), py::bytes(t));
       }, py::arg("off"), py::arg("n"), py::arg("key"), py::arg("nonce"), py::arg("encrypt"), py::arg("tag") = py::bytes(),
          py::arg("request_id") = "")
+      // GET of a whole SSE-S3 object decrypted by the chunkserver (op 11, or op 15 for an RS(k, m) file):
+      // `meta` is the file's encoded FileMetadata; (status, plaintext or None); status 0 done, 1 not
+      // handled (the caller reads its own way), 2 authentication failure
+      .def("sse_read", [](FastClient& c, py::bytes meta, py::bytes key, const std::string& rid) {
+        std::string mp = meta, k = key;
+        if (k.size() != 32) throw std::invalid_argument("sse_read: 32-byte key");
+        int64_t slot = -1;
+        uint64_t n = 0;
+        FastClient::Status st;
+        {
+          py::gil_scoped_release r;
+          st = c.sse_read(mp, reinterpret_cast<const uint8_t*>(k.data()), &slot, &n, rid);
+        }
+        gcm::wipe(&k[0], k.size());
+        py::object data = py::none();
+        if (st == FastClient::Ok) {
+          data = py::bytes(reinterpret_cast<const char*>(c.slot_ptr(slot)), n);
+          c.release(slot);
+        }
+        return py::make_tuple(static_cast<int>(st), data);
+      }, py::arg("meta"), py::arg("key"), py::arg("request_id") = "")
       // PUT of an SSE-S3 object sealed by the chunkserver (op 13): `plaintext` goes into a slot as
       // [12 free][plaintext][16 free]; (status, spent, message, the slot's bytes afterwards); status 0 done,
       // 1 not handled (slot untouched), 2 failed

@@ -2567,6 +2567,7 @@ StoreStats ChunkStore::stats() {
   s.sse_fused_range_reads = sse_fused_range_reads_.load();
   s.sse_fused_writes = sse_fused_writes_.load();
   s.sse_fused_copies = sse_fused_copies_.load();
+  s.sse_fused_ec_reads = sse_fused_ec_reads_.load();
   s.pulled_recvs = pulled_recvs_.load();
   s.pulled_host_appends = pulled_host_appends_.load();
   s.sliced_stages = sliced_stages_.load();
@@ -4337,6 +4338,145 @@ ChunkStore::SseRead ChunkStore::sse_read(const std::string& id, const uint8_t ke
   }
   if (!whole) std::memcpy(out, pt + from, want);
   *n_out = want;
+  return SseRead::Ok;
+}
+
+namespace {
+// The lane's pinned scratch of an sse_ec_read_kernel launch: GHASH partials, nonce and tag, GF tables.
+constexpr uint64_t kSseEcReadNonceTagOff = gcm::kGcmMaxGrid * sizeof(gcm::U128);
+constexpr uint64_t kSseEcReadTablesOff = kSseEcReadNonceTagOff + 32;
+constexpr uint64_t kSseEcReadScratch = kSseEcReadTablesOff + kEcFusedMaxRows * kMaxShards * 32;
+}  // namespace
+
+bool ChunkStore::sse_ec_read_fusable(uint64_t sl, uint64_t orig, const uint8_t* out) {
+  return gpu() && sse_ec_read_fused_enabled() && orig >= 29 && orig - 28 >= sse_ec_read_fused_min_bytes() &&
+         sse_read_tiles(orig - 28) <= (0xFFFFFFFEull >> 10) && sl >= kSseEcReadMinShard &&
+         (!out || (aligned16(out) && device_view(out, orig - 28) != nullptr));
+}
+
+ChunkStore::SseRead ChunkStore::sse_ec_read(const std::vector<const uint8_t*>& shards, int k, int m, uint64_t sl,
+                                            uint64_t orig, const uint8_t key[32], uint8_t* out, uint64_t out_cap,
+                                            uint64_t* n_out, std::string* err, bool fused_only) {
+  TraceRange tr("dfs.store.sse_ec_read");  // no key material in ranges, logs or errors
+  *n_out = 0;
+  if (k <= 0 || m < 0 || k + m > kMaxShards || static_cast<int>(shards.size()) != k + m || sl == 0 || orig > sl * k || !out) {
+    *err = "SSE EC read needs 1..32 shards and a blob inside the data columns";
+    return SseRead::IoError;
+  }
+  if (orig < 29) {
+    *err = "not an SSE blob: " + std::to_string(orig) + " bytes";
+    return SseRead::IoError;
+  }
+  const uint64_t n = orig - 28;
+  if (n > out_cap) {
+    *err = "buffer of " + std::to_string(out_cap) + " bytes for " + std::to_string(n) + " of plaintext";
+    return SseRead::IoError;
+  }
+  std::vector<int> present, missing;  // missing: every lost data column, the tag covers the whole blob
+  for (int i = 0; i < k + m && static_cast<int>(present.size()) < k; ++i)
+    if (shards[i]) present.push_back(i);
+  if (static_cast<int>(present.size()) < k) {
+    *err = "RS reconstruct error: TooFewShardsPresent";
+    return SseRead::IoError;
+  }
+  for (int c = 0; c < k; ++c)
+    if (!shards[c]) missing.push_back(c);
+  const int nr = static_cast<int>(missing.size());
+
+  bool fused = sse_ec_read_fusable(sl, orig) && nr <= kEcFusedMaxRows && aligned16(out);
+  for (int i : present) fused = fused && aligned16(shards[i]);
+  if (fused) HIP_OK(hipSetDevice(cfg_.device));
+  uint8_t* dout = fused ? device_view(out, n) : nullptr;
+  if (dout) {
+    gf::Matrix rows;
+    if (nr) rows = gf::rs_decode_rows(k, m, present, missing);
+    const uint64_t ntiles = sse_read_tiles(n);
+    const gcm::Plan plan = gcm::plan_for(kSseReadTileBytes * ntiles);
+    Lane* l = acquire_lane();
+    ensure_hscratch(l, kSseEcReadScratch);
+    // Nothing below throws: the lane is released and every copy of the key schedule and the powers
+    // of H that the store owns is wiped on each way out. A launch that fails has written nothing,
+    // so the call goes on to the staged route; a failed synchronise is an error.
+    gcm::Keys keys;
+    SseEcReadLaunch a{};
+    hipError_t launched = hipErrorNotReady, synced = hipSuccess;
+    bool authentic = false;
+    if (l->hscratch_dev && gcm::prepare_keyed(key, plan, &keys)) {
+      uint8_t* hdev = static_cast<uint8_t*>(l->hscratch_dev);
+      a.k = k;
+      a.rows = nr;
+      a.sl = sl;
+      for (int j = 0; j < k; ++j) {
+        a.in[j] = shards[present[j]];
+        a.surv_col[j] = static_cast<int8_t>(present[j] < k ? present[j] : -1);
+      }
+      for (int r = 0; r < nr; ++r) a.row_col[r] = static_cast<int8_t>(missing[r]);
+      if (nr) {
+        std::vector<uint8_t> flat(static_cast<size_t>(nr) * k);
+        for (int r = 0; r < nr; ++r)
+          for (int c = 0; c < k; ++c) flat[r * k + c] = rows[r][c];
+        gf_nibble_tables(flat.data(), nr, k, reinterpret_cast<uint32_t*>(l->hscratch + kSseEcReadTablesOff));
+        a.tables = reinterpret_cast<const uint32_t*>(hdev + kSseEcReadTablesOff);
+      }
+      a.out = dout;
+      a.n = n;
+      a.ntiles = ntiles;
+      std::memcpy(a.rk, keys.rk, sizeof(a.rk));
+      a.h = keys.h;
+      a.hjump = keys.hjump;
+      std::memcpy(a.tree, keys.tree, sizeof(a.tree));
+      a.part = reinterpret_cast<gcm::U128*>(hdev);
+      a.nonce_tag = hdev + kSseEcReadNonceTagOff;
+      launched = launch_sse_ec_read(a, dtables_, plan.grid, l->stream);
+      if (launched == hipSuccess) {
+        launches_++;
+        synced = hipStreamSynchronize(l->stream);
+        if (synced == hipSuccess) {
+          // the kernel read, or rebuilt, the nonce where it lies; E_K(J0) and the comparison are the host's
+          const uint8_t* nt = l->hscratch + kSseEcReadNonceTagOff;
+          authentic = gcm::set_nonce(key, nt, &keys) &&
+                      gcm::tag_matches(keys, gcm::ghash_fold(keys, plan, reinterpret_cast<const gcm::U128*>(l->hscratch)),
+                                       n, plan.nblocks - (n + 15) / 16, nt + 12);
+        }
+        gcm::wipe(l->hscratch, plan.grid * sizeof(gcm::U128));
+      }
+    }
+    gcm::wipe(&a, sizeof(a));
+    gcm::wipe(&keys, sizeof(keys));
+    release_lane(l);
+    if (launched == hipSuccess) {
+      if (synced != hipSuccess) {
+        *err = std::string("SSE EC read kernel: ") + hipGetErrorString(synced);
+        return SseRead::IoError;
+      }
+      sse_fused_ec_reads_++;
+      if (authentic) {
+        *n_out = n;
+        return SseRead::Ok;
+      }
+      std::memset(out, 0, n);  // plaintext of a blob that did not authenticate is nobody's
+      *err = kSseAuthFailed;
+      return SseRead::AuthFailed;
+    }
+    (void)hipGetLastError();
+  }
+  if (fused_only) {
+    *err = "the kernel does not take this read";
+    return SseRead::Declined;
+  }
+  // staged: the blob out of the shards into a temporary (ec_read_range's own routes), decrypted
+  // there, and the plaintext copied; GCM authenticates all or nothing
+  std::vector<uint8_t> tmp(orig);
+  if (ec_read_range(shards, k, m, sl, 0, orig, tmp.data(), err) != EcRead::Ok) {
+    if (err->empty()) *err = "EC read of the blob failed";
+    return SseRead::IoError;
+  }
+  if (!sse_crypt(tmp.data() + 12, n, key, tmp.data(), false, tmp.data() + 12 + n, err)) {
+    std::memset(out, 0, n);
+    return *err == kSseAuthFailed ? SseRead::AuthFailed : SseRead::IoError;
+  }
+  std::memcpy(out, tmp.data() + 12, n);
+  *n_out = n;
   return SseRead::Ok;
 }
 

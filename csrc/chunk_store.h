@@ -100,6 +100,7 @@ struct StoreStats {
   uint64_t sse_fused_range_reads = 0;  // of those, byte ranges by sse_read_range_kernel
   uint64_t sse_fused_writes = 0;  // SSE PUTs encrypted, authenticated, checksummed and landed by one sse_write_kernel launch
   uint64_t sse_fused_copies = 0;  // SSE CopyObjects verified, re-keyed, checksummed and landed by one sse_rekey_kernel launch
+  uint64_t sse_fused_ec_reads = 0;  // SSE blobs held as RS shards rebuilt, authenticated, decrypted and delivered by one sse_ec_read_kernel launch
   uint64_t pulled_recvs = 0;  // replica receives moved by the receiver's copy+checksum kernel
   uint64_t pulled_host_appends = 0;  // ... whose journal append read the kernel's host copy
   uint64_t sliced_stages = 0;    // pipelined head writes (per-slice fused kernels, sends overlap)
@@ -351,6 +352,26 @@ class ChunkStore {
   SseRead sse_read(const std::string& id, const uint8_t key[32], uint8_t* out, uint64_t out_cap, uint64_t* n,
                    std::string* err, int64_t* bad_slice = nullptr, bool fused_only = false, uint64_t from = 0,
                    uint64_t want = UINT64_MAX);
+  // A GET of an SSE-S3 object held as an RS(k, m) file: the blob [nonce 12][ciphertext n][tag 16],
+  // orig = n + 28 bytes, is the first `orig` bytes of the k data columns of `sl` bytes; `shards` are
+  // the k + m device pointers as for ec_read_range (nullptr: lost), of which the first k present are
+  // used, and they are taken as verified. The n plaintext bytes end up at out[0, n), *n is set,
+  // out_cap >= n, and nothing behind out + n is written. On a GPU store with `out` registered and
+  // 16 B aligned, every used shard 16 B aligned, sl >= kSseEcReadMinShard, at most kEcFusedMaxRows
+  // lost data columns, the route on and n at or above sse_ec_read_fused_min_bytes(): one
+  // sse_ec_read_kernel launch rebuilds the lost columns, authenticates, decrypts and stores the
+  // plaintext. Otherwise, and after a launch that failed, the staged route: ec_read_range of
+  // [0, orig) into a temporary, sse_crypt there, and a copy of the plaintext. Statuses and bytes are
+  // the same either way: AuthFailed has *err = kSseAuthFailed and leaves out[0, n) zeroed, fewer than
+  // k shards is IoError, and with fused_only the call answers Declined instead of taking the staged
+  // route. The key schedule and the powers of H are wiped before this returns.
+  // What of that is known before any shard is at hand (the fast path asks before it gathers): a GPU
+  // store, the route on, the shard length, the plaintext's floor and, with `out` given, a registered
+  // and 16 B aligned destination.
+  bool sse_ec_read_fusable(uint64_t sl, uint64_t orig, const uint8_t* out = nullptr);
+  SseRead sse_ec_read(const std::vector<const uint8_t*>& shards, int k, int m, uint64_t sl, uint64_t orig,
+                      const uint8_t key[32], uint8_t* out, uint64_t out_cap, uint64_t* n, std::string* err,
+                      bool fused_only = false);
   // A PUT of an SSE-S3 object: buf[0, n + 28) holds the plaintext at buf + 12 (what stands in the
   // other 28 bytes does not matter), n >= 1. Afterwards buf holds the blob [nonce][ciphertext][tag]
   // and block `id` is stored exactly as write(id, buf, n + 28, 0) would have stored it: same bytes,
@@ -594,7 +615,8 @@ class ChunkStore {
                 std::vector<uint32_t>* crc, std::string* err, const uint8_t* block = nullptr, uint64_t n = 0);
   const uint8_t* sse_read_pin(const std::string& id, const uint8_t* out, uint64_t* size, uint64_t from, uint64_t want);
   std::atomic<uint64_t> ec_fused_encodes_{0}, ec_fused_decodes_{0}, ec_fused_reads_{0}, ec_fused_converts_{0},
-      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0}, sse_fused_writes_{0}, sse_fused_copies_{0};
+      sse_fused_crypts_{0}, sse_fused_reads_{0}, sse_fused_range_reads_{0}, sse_fused_writes_{0}, sse_fused_copies_{0},
+      sse_fused_ec_reads_{0};
   const uint8_t* sse_copy_pin(const std::string& src_id, const std::string& dst_id, uint64_t* size);
   std::atomic<uint64_t> direct_dma_{0}, staged_dma_{0};
   std::unique_ptr<GroupSync> gsync_;

@@ -853,12 +853,50 @@ FastClient::Status FastClient::sse_read(const std::string& meta_pb, const uint8_
   RequestScope rs(rid);
   if (!base_) return NotHandled;
   pb::FileMetadata m;
-  if (!m.decode(meta_pb) || m.blocks.size() != 1 || m.blocks[0].ec_data_shards > 0 || m.size < 29 || m.size > slot_bytes_)
-    return NotHandled;
+  if (!m.decode(meta_pb) || m.blocks.size() != 1 || m.size < 29 || m.size > slot_bytes_) return NotHandled;
   const bool ranged = want != UINT64_MAX;
   if (ranged && (want == 0 || from > m.size - 28 || want > m.size - 28 - from)) return NotHandled;
   if (lead) *lead = ranged ? from % 16 : 0;
   const pb::BlockInfo& b = m.blocks[0];
+  if (b.ec_data_shards > 0) {
+    // an RS(k, m) file: the co-located chunkserver gathers the surviving shards into its HBM and one
+    // kernel rebuilds, authenticates and decrypts them (fast-path op 15); whole objects only
+    const int k = b.ec_data_shards, mm = b.ec_parity_shards;
+    const uint64_t orig = b.original_size ? b.original_size : m.size;
+    if (ranged || local_cs_.empty() || mm <= 0 || b.locations.size() != static_cast<size_t>(k + mm) || orig != m.size)
+      return NotHandled;
+    const int64_t s = acquire(slot_bytes_);
+    if (s < 0) return NotHandled;
+    std::string body;
+    put<uint16_t>(body, static_cast<uint16_t>(k));
+    put<uint16_t>(body, static_cast<uint16_t>(mm));
+    put<uint64_t>(body, (orig + k - 1) / k);
+    put<uint64_t>(body, orig);
+    put<uint64_t>(body, static_cast<uint64_t>(s));
+    put<uint64_t>(body, slot_bytes_);
+    put_str(body, b.block_id);
+    put<uint16_t>(body, 32);  // straight into `body`, which is wiped: no temporary holds the key
+    body.append(reinterpret_cast<const char*>(key), 32);
+    put_str(body, arena_path_);
+    put<uint16_t>(body, static_cast<uint16_t>(k + mm));
+    for (auto& a : b.locations) put_str(body, strip_scheme(a));
+    put_str(body, rid);
+    uint8_t st = 0;
+    uint64_t total = 0, got = 0;
+    std::string fmsg;
+    const bool sent = fp_call(15, body, &st, &total, &got, &fmsg);
+    gcm::wipe(&body[0], body.size());
+    if (!sent || st != 0 || got + 28 != orig) {
+      release(s);
+      return sent && st == 9 ? Failed : NotHandled;  // FpStatus::AuthFailed is final; anything else is the caller's own read
+    }
+    *slot = s;
+    *n = got;
+    reads_++;
+    sse_gpu_++;
+    ec_dev_reads_++;
+    return Ok;
+  }
   bool local = false;
   for (auto& l : b.locations) local |= strip_scheme(l) == local_cs_;
   if (!local) return NotHandled;

@@ -150,7 +150,9 @@ class FastClient {
   // bytes at the front of *slot (the caller releases it). Failed: the tag does not match, which is
   // final. NotHandled: no slot is held and the caller reads and decrypts as before. With `want`
   // given, op 12: plaintext [from, from + want) alone, *n = want, its first byte *lead = from % 16
-  // bytes into the slot (0 for the whole object).
+  // bytes into the slot (0 for the whole object). A single-block RS(k, m) file goes by op 15, whole
+  // objects only: the chunkserver gathers the surviving shards and one kernel rebuilds, authenticates
+  // and decrypts them, or declines before gathering anything.
   Status sse_read(const std::string& meta_pb, const uint8_t key[32], int64_t* slot, uint64_t* n, const std::string& rid,
                   uint64_t from = 0, uint64_t want = UINT64_MAX, uint64_t* lead = nullptr);
   // CopyObject of the stored SSE-S3 blob that `src_meta_pb` describes (one block on the co-located

@@ -45,6 +45,7 @@ Json stats_json(const StoreStats& t) {
   d.set("sse_fused_range_reads", t.sse_fused_range_reads);
   d.set("sse_fused_writes", t.sse_fused_writes);
   d.set("sse_fused_copies", t.sse_fused_copies);
+  d.set("sse_fused_ec_reads", t.sse_fused_ec_reads);
   d.set("pulled_recvs", t.pulled_recvs);
   d.set("pulled_host_appends", t.pulled_host_appends);
   d.set("sliced_stages", t.sliced_stages);
@@ -147,6 +148,7 @@ Json stats_json(const FpStats& t) {
   d.set("fp_sse_reads", t.sse_reads);
   d.set("fp_sse_writes", t.sse_writes);
   d.set("fp_sse_copies", t.sse_copies);
+  d.set("fp_sse_ec_reads", t.sse_ec_reads);
   d.set("fp_heals_out", t.heals_out);
   d.set("fp_heals_in", t.heals_in);
   d.set("fp_sliced_writes", t.sliced_writes);

@@ -1112,6 +1112,9 @@ void FastPathServer::serve(int fd) {
       sent = ec_write(fd, body.data() + 1, body.data() + n);
     } else if (op == 8) {  // EC_READ: gather the surviving shards into HBM, decode there
       sent = ec_read(fd, body.data() + 1, body.data() + n);
+    } else if (op == 15) {  // SSE_EC_READ: gather the surviving shards of an SSE-S3 blob, rebuild and decrypt in one kernel
+      sent = sse_ec_read(fd, body.data() + 1, body.data() + n);
+      gcm::wipe(body.data(), body.size());
     } else if (op == 9) {  // PUSH: a local block to a peer over the engine (EC gathers)
       sent = push_block(fd, body.data() + 1, body.data() + n);
     } else if (op == 5) {  // CTRL: replication pair bring-up / rebuild
@@ -1433,6 +1436,65 @@ bool FastPathServer::ec_read(int fd, const uint8_t* body, const uint8_t* end) {
     if (missing > 0) st_.ec_device_decodes++;
   }
   return ok ? send_response(fd, FpStatus::Ok, orig, want, "") : send_response(fd, FpStatus::IoError, 0, 0, "copy out failed");
+}
+
+bool FastPathServer::sse_ec_read(int fd, const uint8_t* body, const uint8_t* end) {
+  Reader rd{body, end};
+  uint16_t k = rd.get<uint16_t>(), m = rd.get<uint16_t>();
+  uint64_t sl = rd.get<uint64_t>(), orig = rd.get<uint64_t>(), shm_off = rd.get<uint64_t>(), cap = rd.get<uint64_t>();
+  std::string id = rd.str(), key = rd.str(), path = rd.str();
+  std::vector<std::string> locs = read_list(rd, false);
+  std::string rid = rd.p < rd.end ? rd.str() : std::string();
+  RequestScope rs(rid);
+  note_rid(rid);
+  TraceRange tr("dfs.fp.sse_ec_read");  // the key stays out of ranges, logs and answers
+  bool sent;
+  std::string err;
+  uint8_t* base = nullptr;
+  if (!rd.ok || id.empty() || key.size() != 32 || k == 0 || m == 0 || k + m > kMaxShards || locs.size() != size_t(k) + m ||
+      sl == 0 || sl > kMaxTransfer || orig < 29 || orig > sl * k || cap == 0 || cap > kMaxTransfer || shm_off > (1ull << 62)) {
+    sent = send_response(fd, FpStatus::BadRequest, 0, 0, "malformed sse ec read request");
+  } else if (!store_->sse_ec_read_fusable(sl, orig)) {  // known from the request: nothing is gathered for a read the kernel declines
+    sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU, shards too short or below the kernel's floor");
+  } else if (orig - 28 > cap || (base = map_shm(path, shm_off, cap, &err)) == nullptr) {
+    sent = send_response(fd, FpStatus::Unsupported, 0, 0, orig - 28 > cap ? "slot too small" : "short-circuit unavailable: " + err);
+  } else {
+    if (store_->gpu()) {  // a new arena is pinned off this thread: the first read waits for that instead of losing the GPU
+      std::unique_lock<std::mutex> lk(mu_);
+      workers_cv_.wait(lk, [this] { return pending_regs_ == 0; });
+    }
+    EcGather g;
+    int present = 0;
+    // a slot the kernel cannot reach is known now too: nothing is gathered for it either
+    const bool reachable = store_->sse_ec_read_fusable(sl, orig, base + shm_off);
+    if (reachable && ec_gather(id, locs, sl, -1, k, &g, &err))
+      for (int i = 0; i < k + m; ++i) present += g.ptrs[i] != nullptr;
+    if (!reachable) {
+      sent = send_response(fd, FpStatus::Unsupported, 0, 0, "slot not pinned or not 16 B aligned");
+    } else if (present < k) {
+      sent = send_response(fd, FpStatus::Unsupported, 0, 0, "surviving shards not gathered: " + err);
+    } else {
+      const std::vector<const uint8_t*> shards(g.ptrs.begin(), g.ptrs.begin() + k + m);
+      uint64_t n = 0;
+      // the kernel or nothing: declined means the slot is as the client left it
+      switch (store_->sse_ec_read(shards, k, m, sl, orig, reinterpret_cast<const uint8_t*>(key.data()), base + shm_off, cap,
+                                  &n, &err, true)) {
+        case ChunkStore::SseRead::Ok: {
+          std::lock_guard<std::mutex> lk(mu_);
+          st_.sse_ec_reads++;
+        }
+          sent = send_response(fd, FpStatus::Ok, orig, n, "");
+          break;
+        case ChunkStore::SseRead::AuthFailed: sent = send_response(fd, FpStatus::AuthFailed, 0, 0, err); break;
+        case ChunkStore::SseRead::Declined:
+          sent = send_response(fd, FpStatus::Unsupported, 0, 0, "no GPU, slot not pinned, shards too short or below the kernel's floor");
+          break;
+        default: sent = send_response(fd, FpStatus::IoError, 0, 0, err); break;
+      }
+    }
+  }
+  gcm::wipe(&key[0], key.size());
+  return sent;
 }
 
 }  // namespace dfs

@@ -72,6 +72,15 @@
 //               ChunkStore::sse_copy_fusable says no, or some server of `next` has no device P2P pair up
 //               (with no slot there is no shared-memory fallback, so that replica would only be counted
 //               as failed): the client then copies its own way.
+//     op 15 SSE_EC_READ: u16 k | u16 m | u64 shard_len | u64 orig | u64 shm_off | u64 shm_cap | u16 id | u16 key(32)
+//               | u16 path | u16 n | (u16 len addr)* ("" = lost) [| u16 rid]  -- GET of an SSE-S3 object held as
+//               an RS(k, m) file, whole object only: the surviving shards gathered into this GPU as op 8
+//               gathers them, then sse_ec_read_kernel rebuilds the lost columns, authenticates, decrypts and
+//               stores only the plaintext at the front of the client's slot. Answers as op 11: Ok with
+//               total = orig and bytes = orig - 28, AuthFailed (final), or Unsupported when
+//               ChunkStore::sse_ec_read_fusable says no (asked before anything is gathered), the gather is
+//               unavailable or ChunkStore::sse_ec_read declines: the client then reads and decrypts its
+//               own way.
 //   response = u32 body_len | u8 status | u64 total | u64 bytes | u16 msg_len msg
 //   (for WRITE/REPL ``bytes`` carries replicas_written; for CTRL ``msg`` is the engine reply)
 //
@@ -123,6 +132,7 @@ struct FpStats {
   uint64_t sse_reads = 0;         // stored SSE blobs decrypted into clients' slots by one kernel
   uint64_t sse_writes = 0;        // SSE bodies encrypted in clients' slots and stored by one kernel
   uint64_t sse_copies = 0;        // stored SSE blobs re-keyed into new blocks by one kernel
+  uint64_t sse_ec_reads = 0;      // SSE blobs held as RS shards gathered, rebuilt and decrypted into clients' slots by one kernel
   uint64_t heals_out = 0, heals_in = 0;  // heal / balancer copies sent / received on the engine
   uint64_t sliced_writes = 0;  // head writes whose replica sends overlapped the staging
   // device-resident erasure coding: EC writes whose shards were encoded and scattered HBM ->
@@ -243,6 +253,7 @@ class FastPathServer {
   // op 7 / op 8 / op 9 bodies (answered on fd)
   bool ec_write(int fd, const uint8_t* body, const uint8_t* end);
   bool ec_read(int fd, const uint8_t* body, const uint8_t* end);
+  bool sse_ec_read(int fd, const uint8_t* body, const uint8_t* end);
   bool push_block(int fd, const uint8_t* body, const uint8_t* end);
   // Pipelined head write of a large replicated block; false = not applicable (the caller
   // takes the stage-then-forward path), true = answered on `fd` (*sent = write result).

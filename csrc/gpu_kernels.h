@@ -29,6 +29,9 @@
 //   K7 copy  sse_rekey_kernel: a CopyObject of an SSE-S3 object in one pass from one HBM extent to
 //          another — the source's slices verified and its ciphertext authenticated, both keystreams
 //          XORed into it in registers, the new ciphertext authenticated, checksummed and stored.
+//   K7 + K5 read  sse_ec_read_kernel: a GET of an SSE-S3 object held as RS(k, m) shards — the k
+//          surviving shards loaded as the blob they spell (lost columns rebuilt in registers), the
+//          ciphertext authenticated and decrypted there, and only the plaintext stored over PCIe.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -436,6 +439,50 @@ bool sse_copy_fused_enabled();
 uint64_t sse_copy_fused_min_bytes();
 void set_sse_copy_fused(bool on, int64_t min_bytes = -1);
 hipError_t launch_sse_rekey(const SseRekeyLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
+
+// K7 EC read (sse_ec_read_kernel): the stored blob [nonce 12][ciphertext n][tag 16], orig = n + 28
+// bytes, is held as an RS(k, m) file with sl >= ceil(orig / k): blob byte x is byte x % sl of data
+// column x / sl, zeros from orig on. `in` are k surviving shards in HBM (16 B aligned, sl bytes in
+// buffers padded to 16 B), `surv_col`, `row_col` and `tables` as EcReadLaunch carries them, and every
+// data column is either a survivor or named by a reconstruct row. The n plaintext bytes go to `out`,
+// the 16 B aligned device view of registered host memory: exactly [out, out + n) is written. The
+// rest is SseReadLaunch's without the checksum fields: the plan gcm::plan_for(kSseReadTileBytes *
+// ntiles), ntiles = sse_read_tiles(n), whose grid is the launch's, gcm::prepare_keyed's key schedule
+// and powers of H, `part` for gcm::ghash_fold and `nonce_tag` for gcm::tag_matches (device-visible
+// host words, like `tables`). The shards are not checksummed here: the caller hands over verified
+// shards, and the tag authenticates what was rebuilt and decrypted.
+// The minimum shard length is one wave's span of the axis (64 lanes x 64 B): then a wave's blocks lie in
+// at most two columns, which bounds the load stage's passes and lets the second one reuse the first
+// one's registers. Shorter shards (blobs under 4 KiB * k) take the staged route.
+constexpr uint64_t kSseEcReadMinShard = 4096;
+static_assert(kSseEcReadMinShard >= kEcReadMinShard && kSseEcReadMinShard <= kSseReadTileBytes, "between the two");
+struct SseEcReadLaunch {
+  const uint8_t* in[kMaxShards];
+  int8_t surv_col[kMaxShards];      // data column that survivor j is, -1 for a parity shard
+  int8_t row_col[kEcFusedMaxRows];  // data column that reconstruct row r rebuilds
+  int k, rows;
+  uint64_t sl;
+  const uint32_t* tables;  // [rows][k] x 8 dwords; unused when rows == 0
+  uint8_t* out;
+  uint64_t n, ntiles;
+  uint32_t rk[60];
+  gcm::U128 h, hjump, tree[gcm::kGcmTreeSteps];
+  gcm::U128* part;     // [grid]
+  uint8_t* nonce_tag;  // [28]
+};
+// DFS_SSE_EC_READ_FUSED=0 keeps the staged route (ec_read_range of the blob into a temporary, then
+// sse_crypt or OpenSSL there), and blobs whose plaintext is below sse_ec_read_fused_min_bytes() stay
+// on it. DFS_SSE_EC_READ_FUSED_MIN_BYTES overrides the floor; set_sse_ec_read_fused is the benches'
+// and tests' switch (min_bytes < 0 keeps it). Measured (profiles/r15/README.md, RS(6,3), against
+// ec_read_range of the blob into the slot followed by sse_crypt there), a call costs ~129 us at 64 KiB,
+// which the staged pair undercuts (32 us: OpenSSL under sse_crypt's floor); 1 MiB is the smallest
+// measured size the kernel wins (151 against 202 us, spreads under 2 us), with 0 and with 1 lost data
+// column alike. No size between 64 KiB and 1 MiB was taken.
+constexpr uint64_t kSseEcReadFusedMinBytes = 1ull << 20;
+bool sse_ec_read_fused_enabled();
+uint64_t sse_ec_read_fused_min_bytes();
+void set_sse_ec_read_fused(bool on, int64_t min_bytes = -1);
+hipError_t launch_sse_ec_read(const SseEcReadLaunch& a, const DevCrcTables* t, int grid, hipStream_t s);
 hipError_t launch_scrub(const ScrubLaunch& a, const DevCrcTables* t, hipStream_t s);
 
 }  // namespace dfs

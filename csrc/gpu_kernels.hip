@@ -2789,6 +2789,276 @@ __global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2
   }
 }
 
+// ---- K7 EC read: a GET of an SSE-S3 object held as RS(k, m) shards, in one pass ----
+//
+// The stored blob [nonce 12][ciphertext n][tag 16] is not in HBM as one extent: blob byte x is byte
+// x % sl of data column x / sl, and a column is either a surviving shard or the GF(2^8) product of
+// the k survivors. The kernel treats the shards as the blob: it has sse_read_kernel's tiles (16 KiB
+// of the axis per workgroup step, thread t owns AES blocks 1024 T + 4t .. + 3, the plan
+// gcm::plan_for(16 KiB * ntiles)), its AES, its GHASH and its stores, and in front of them a load
+// stage that builds a thread's four ciphertext blocks out of shard vectors.
+//
+// Virtual-blob load. AES block q is blob bytes [16q + 12, 16q + 28). Byte p of column c is blob byte
+// c * sl + p, so on the AES axis the column starts at delta = c * sl - 12, and with q and the
+// shard's vector index v both on 16 B grids the only per-column quantity is the byte shift
+// delta & 15: block q takes its low `shift` bytes from the top of shard vector v - 1 and the rest
+// from the bottom of v, v = q - (delta >> 4). The 12 bytes between the blob's vector grid and the
+// AES blocks are part of that shift, not a second funnel. A wave (64 threads, 4 KiB of the axis) walks
+// the columns that its span touches with a wave-uniform c, shard pointer and shift: a thread loads
+// its four aligned vectors of the shard, takes vector v - 1 from the lane below (lane_below; lane 0
+// loads that one vector itself) and funnels with v_alignbyte_b32. The bytes that fall outside the
+// column's window [delta, delta + sl) are masked off and the passes ORed, which is how a thread, or
+// a block, that straddles a column boundary merges its two columns. The shard pointers are only
+// ever indexed with the wave-uniform column (scalar loads from the kernel arguments).
+//   With sl >= kSseEcReadMinShard = 4 KiB a wave's span touches at most two columns; the first one's
+// vectors for the workgroup's next tile are loaded before the current tile is decrypted.
+//
+// Lost columns. A pass over a lost column builds the same five vectors as the product of reconstruct
+// row r with the k survivors' vectors at the same indices (split-nibble v_perm_b32 form, the row's
+// tables broadcast from LDS, the next survivor's loads issued before the current one's arithmetic).
+// Because the axis is the blob's, a span never needs two rebuilt columns at the same shard position,
+// so one set of accumulators (five vectors, the fifth live in lane 0 only) serves any number of lost
+// columns: the template argument only says whether the rebuild exists. Parity survivors are only
+// ever multiplied. Every column is rebuilt, the tag covers the whole blob.
+//
+// Nonce and tag. The nonce is vector 0 of column 0: a scalar load where that column survives, else
+// k uniform 16 B loads and one product, which every thread of the workgroup does alike (the loads are
+// of one and the same vector, and nothing has to be shared through LDS). The stored tag is AES-axis bytes [n, n + 16):
+// the threads whose blocks hold them store them to `nonce_tag` from the merged registers, so it may
+// lie in a rebuilt column or across a boundary.
+//
+// No CRC stage: as with ec_read_kernel the caller hands over verified shards (the gather scrubs the
+// local one, peers' shards are checksummed as they land), and the GCM tag authenticates the result.
+// The compiler's report (-Rpass-analysis=kernel-resource-usage, gfx950):
+//   rebuild  VGPRs  SGPRs  SGPR spills           scratch  LDS bytes  waves per SIMD
+//   no        137    106    15 (to VGPR lanes)      0       1376     2
+//   yes       231    105     0                      0       5472     2
+struct ColVecs {
+  uint4 v[4];
+  uint4 below;  // lane 0: the vector under v[0]
+};
+
+// Block bytes [16v - shift, 16v - shift + 16) of a shard: the top `shift` bytes of vector v - 1 under
+// the low 16 - shift of vector v. `shift` is wave-uniform.
+__device__ __forceinline__ uint4 shift_up(const uint4& prev, const uint4& cur, uint32_t shift) {
+  if (!shift) return cur;
+  const uint32_t w = (16u - shift) >> 2, b = (16u - shift) & 3u;
+  uint32_t e0, e1, e2, e3, e4;
+  switch (w) {
+    case 0: e0 = prev.x; e1 = prev.y; e2 = prev.z; e3 = prev.w; e4 = cur.x; break;
+    case 1: e0 = prev.y; e1 = prev.z; e2 = prev.w; e3 = cur.x; e4 = cur.y; break;
+    case 2: e0 = prev.z; e1 = prev.w; e2 = cur.x; e3 = cur.y; e4 = cur.z; break;
+    default: e0 = prev.w; e1 = cur.x; e2 = cur.y; e3 = cur.z; e4 = cur.w; break;
+  }
+  return make_uint4(__builtin_amdgcn_alignbyte(e1, e0, b), __builtin_amdgcn_alignbyte(e2, e1, b),
+                    __builtin_amdgcn_alignbyte(e3, e2, b), __builtin_amdgcn_alignbyte(e4, e3, b));
+}
+
+__device__ __forceinline__ void gf_mul_add(const uint32_t (&tb)[8], const uint4& d, uint4& acc) {
+  acc.x ^= gf_mul4(tb, nibble_sel(d.x));
+  acc.y ^= gf_mul4(tb, nibble_sel(d.y));
+  acc.z ^= gf_mul4(tb, nibble_sel(d.z));
+  acc.w ^= gf_mul4(tb, nibble_sel(d.w));
+}
+
+constexpr int kColNone = -128;  // col_src: a column that nothing supplies (the launch refuses it)
+
+template <bool kRebuild>
+__global__ __launch_bounds__(kCrcWgThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void sse_ec_read_kernel(
+    SseEcReadLaunch a, const DevCrcTables* __restrict__ gt) {
+  static_assert(kCrcWgThreads == 256 && gcm::kGcmTileBlocks * 16 == kSseReadTileBytes, "sse_read_kernel's tiles");
+  static_assert(kSseEcReadMinShard >= 16 * gcm::kGcmWaveBlocks, "a wave's span touches at most two columns");
+  __shared__ uint32_t te0[256];
+  __shared__ uint8_t sbox[256];
+  __shared__ gcm::U128 wave_part[4];
+  __shared__ int8_t col_src[kMaxShards];  // column c: survivor j >= 0, or -1 - r for reconstruct row r
+  __shared__ uint32_t gft[kRebuild ? kEcFusedMaxRows * kMaxShards * 8 : 1];
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), k = a.k;
+  const int64_t n = static_cast<int64_t>(a.n), sl = static_cast<int64_t>(a.sl), nvec = (sl + 15) / 16;
+
+  sse_load_tables(gt, te0, sbox);
+  if (threadIdx.x < static_cast<unsigned>(k)) {
+    int src = kColNone;
+    for (int j = 0; j < k; ++j)
+      if (a.surv_col[j] == static_cast<int>(threadIdx.x)) src = j;
+    for (int r = 0; r < a.rows; ++r)
+      if (a.row_col[r] == static_cast<int>(threadIdx.x)) src = -1 - r;
+    col_src[threadIdx.x] = static_cast<int8_t>(src);
+  }
+  if constexpr (kRebuild)
+    for (int i = threadIdx.x; i < a.rows * k * 8; i += kCrcWgThreads) gft[i] = a.tables[i];
+  __syncthreads();
+
+  auto load = [&](const u32x4* base, int64_t v) {
+    uint4 d = make_uint4(0, 0, 0, 0);
+    if (v >= 0 && v < nvec) {  // inside the shard's padded buffer
+      const u32x4 x = __builtin_nontemporal_load(base + v);
+      d = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    return d;
+  };
+  // survivor j's vectors v0 .. v0 + 3 and, in lane 0, v0 - 1
+  auto fetch = [&](int j, int64_t v0, ColVecs& r) {
+    const u32x4* base = reinterpret_cast<const u32x4*>(a.in[j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.v[i] = load(base, v0 + i);
+    r.below = lane == 0 ? load(base, v0 - 1) : make_uint4(0, 0, 0, 0);
+  };
+  auto zero = [](ColVecs& r) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.v[i] = make_uint4(0, 0, 0, 0);
+    r.below = make_uint4(0, 0, 0, 0);
+  };
+  auto source_of = [&](int c) { return __builtin_amdgcn_readfirstlane(static_cast<int>(col_src[c])); };
+  auto first_block = [&](uint64_t tile) { return static_cast<int64_t>(tile * gcm::kGcmTileBlocks + 4 * threadIdx.x); };
+  // the columns that the wave's 4 KiB of tile `tile` touch: blob bytes [x0, x0 + 4096)
+  auto span = [&](uint64_t tile, int& c_lo, int& c_hi) {
+    const int64_t x0 = static_cast<int64_t>(tile * kSseReadTileBytes) + 16 * gcm::kGcmWaveBlocks * wave + 12;
+    c_lo = static_cast<int>(min(x0 / sl, static_cast<int64_t>(k)));
+    c_hi = static_cast<int>(min((x0 + 16 * gcm::kGcmWaveBlocks - 1) / sl, static_cast<int64_t>(k - 1)));
+  };
+  // the thread's first shard vector of column c
+  auto first_vector = [&](uint64_t tile, int c) { return first_block(tile) - ((c * sl - 12) >> 4); };
+  // the vectors of the wave's first column of a tile, where a survivor holds it
+  auto prefetch = [&](uint64_t tile, ColVecs& r) {
+    zero(r);
+    int c_lo, c_hi;
+    span(tile, c_lo, c_hi);
+    if (c_lo > c_hi) return;
+    const int src = source_of(c_lo);
+    if (src >= 0) fetch(src, first_vector(tile, c_lo), r);
+  };
+
+  // the nonce: blob bytes [0, 12), the head of column 0
+  uint32_t n0 = 0, n1 = 0, n2 = 0;
+  {
+    const int src = source_of(0);
+    if (src >= 0) {
+      const uint32_t* head = reinterpret_cast<const uint32_t*>(a.in[src]);
+      n0 = head[0];
+      n1 = head[1];
+      n2 = head[2];
+    } else if constexpr (kRebuild) {
+      if (src != kColNone) {
+        uint4 acc = make_uint4(0, 0, 0, 0);
+        for (int j = 0; j < k; ++j) {
+          uint32_t tb[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) tb[q] = gft[((-1 - src) * k + j) * 8 + q];
+          gf_mul_add(tb, load(reinterpret_cast<const u32x4*>(a.in[j]), 0), acc);
+        }
+        n0 = __builtin_amdgcn_readfirstlane(acc.x);
+        n1 = __builtin_amdgcn_readfirstlane(acc.y);
+        n2 = __builtin_amdgcn_readfirstlane(acc.z);
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 12) {
+    const uint32_t w = threadIdx.x < 4 ? n0 : threadIdx.x < 8 ? n1 : n2;
+    a.nonce_tag[threadIdx.x] = static_cast<uint8_t>(w >> (8 * (threadIdx.x & 3)));
+  }
+
+  gcm::U128 acc{0, 0};
+  ColVecs cur;
+  prefetch(blockIdx.x, cur);
+  for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    ColVecs nxt;
+    zero(nxt);
+    if (tile + gridDim.x < a.ntiles) prefetch(tile + gridDim.x, nxt);
+    const int64_t g = first_block(tile);
+
+    // the ciphertext of blocks g .. g + 3, column by column
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m[i] = 0;
+    int c_lo, c_hi;
+    span(tile, c_lo, c_hi);
+    for (int c = c_lo; c <= c_hi; ++c) {
+      const int src = source_of(c);
+      const int64_t delta = c * sl - 12, v0 = first_vector(tile, c);
+      ColVecs x;
+      if (src >= 0) {
+        if (c == c_lo) x = cur;
+        else fetch(src, v0, x);
+      } else {
+        zero(x);
+        if constexpr (kRebuild) {
+          if (src != kColNone) {
+            const uint32_t* row = gft + (-1 - src) * k * 8;
+            ColVecs d;
+            fetch(0, v0, d);
+            for (int j = 0; j < k; ++j) {
+              ColVecs dn;
+              if (j + 1 < k) fetch(j + 1, v0, dn);
+              uint32_t tb[8];
+#pragma unroll
+              for (int q = 0; q < 8; ++q) tb[q] = row[j * 8 + q];
+#pragma unroll
+              for (int i = 0; i < 4; ++i) gf_mul_add(tb, d.v[i], x.v[i]);
+              gf_mul_add(tb, d.below, x.below);
+              if (j + 1 < k) d = dn;
+            }
+          }
+        }
+      }
+      const uint32_t shift = static_cast<uint32_t>(delta) & 15u;
+      uint4 blk[4];
+      {
+        const uint4 under = make_uint4(lane_below(x.v[3].x, x.below.x), lane_below(x.v[3].y, x.below.y),
+                                       lane_below(x.v[3].z, x.below.z), lane_below(x.v[3].w, x.below.w));
+        blk[0] = shift_up(under, x.v[0], shift);
+#pragma unroll
+        for (int i = 1; i < 4; ++i) blk[i] = shift_up(x.v[i - 1], x.v[i], shift);
+      }
+      const uint32_t w[16] = {blk[0].x, blk[0].y, blk[0].z, blk[0].w, blk[1].x, blk[1].y, blk[1].z, blk[1].w,
+                              blk[2].x, blk[2].y, blk[2].z, blk[2].w, blk[3].x, blk[3].y, blk[3].z, blk[3].w};
+      // the column's window on the AES axis is [delta, delta + sl)
+      const int64_t y = 16 * g;
+      if (y >= delta && y + 64 <= delta + sl) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m[i] = w[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          m[i] |= w[i] & sse_keep(delta + sl - y - 4 * i) & ~sse_keep(delta - y - 4 * i);
+      }
+    }
+
+    // the stored tag, AES-axis bytes [n, n + 16), for the host
+    if (16 * g + 64 > n && 16 * g < n + 16) {
+#pragma unroll
+      for (int i = 0; i < 64; ++i) {
+        const int64_t y = 16 * g + i;
+        if (y >= n && y < n + 16) a.nonce_tag[12 + (y - n)] = static_cast<uint8_t>(m[i >> 2] >> (8 * (i & 3)));
+      }
+    }
+
+    uint32_t ks[4][4];
+    sse_keystream(te0, sbox, a.rk, n0, n1, n2, g, ks);
+
+    if (tile != blockIdx.x) acc = gcm::gf128_mul(a.hjump, acc);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t pos = 16 * (g + b);  // of the block in the message and in `out`
+      uint32_t c[4], o[4];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        c[kk] = m[4 * b + kk] & sse_keep(n - pos - 4 * kk);
+        o[kk] = m[4 * b + kk] ^ ks[b][kk];
+      }
+      acc = ghash_absorb(acc, a.h, c);
+      if (pos + 16 <= n) {
+        *reinterpret_cast<uint4*>(a.out + pos) = make_uint4(o[0], o[1], o[2], o[3]);
+      } else {
+        for (int64_t p = pos; p < n; ++p) a.out[p] = static_cast<uint8_t>(o[(p - pos) >> 2] >> (8 * ((p - pos) & 3)));
+      }
+    }
+    cur = nxt;
+  }
+  ghash_wg_partial(acc, a.tree, wave_part, a.part);
+}
+
 }  // namespace
 
 // Raw CRC (zero init, no xorout) of a 64-byte message whose only set bit is bit p of byte b.
@@ -3430,6 +3700,57 @@ hipError_t launch_sse_rekey(const SseRekeyLaunch& a, const DevCrcTables* t, int 
     return hipErrorInvalidValue;
   if (src < dst + span && dst < src + span) return hipErrorInvalidValue;  // two extents, never one in place
   hipLaunchKernelGGL(sse_rekey_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcWgThreads), 0, s, a, t);
+  return hipGetLastError();
+}
+
+static std::atomic<int> g_sse_ec_read_fused{-1};
+// -1 = DFS_SSE_EC_READ_FUSED_MIN_BYTES, else kSseEcReadFusedMinBytes
+static std::atomic<int64_t> g_sse_ec_read_min_bytes{-1};
+
+void set_sse_ec_read_fused(bool on, int64_t min_bytes) {
+  g_sse_ec_read_fused.store(on ? 1 : 0);
+  if (min_bytes >= 0) g_sse_ec_read_min_bytes.store(min_bytes);
+}
+
+uint64_t sse_ec_read_fused_min_bytes() {
+  int64_t v = g_sse_ec_read_min_bytes.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_EC_READ_FUSED_MIN_BYTES");
+    g_sse_ec_read_min_bytes.store(v = e && std::atoll(e) >= 0 ? std::atoll(e) : static_cast<int64_t>(kSseEcReadFusedMinBytes));
+  }
+  return static_cast<uint64_t>(v);
+}
+
+bool sse_ec_read_fused_enabled() {
+  int v = g_sse_ec_read_fused.load();
+  if (v < 0) {
+    const char* e = std::getenv("DFS_SSE_EC_READ_FUSED");
+    g_sse_ec_read_fused.store(v = (e && std::atoi(e) == 0) ? 0 : 1);
+  }
+  return v != 0;
+}
+
+hipError_t launch_sse_ec_read(const SseEcReadLaunch& a, const DevCrcTables* t, int grid, hipStream_t s) {
+  const gcm::Plan p = gcm::plan_for(kSseReadTileBytes * sse_read_tiles(a.n));
+  if (!t || !a.out || !a.part || !a.nonce_tag || a.n == 0 || a.k <= 0 || a.k > kMaxShards || a.rows < 0 ||
+      a.rows > kEcFusedMaxRows || a.sl < kSseEcReadMinShard || a.n + 28 > a.sl * a.k || (a.rows && !a.tables) ||
+      p.nblocks > 0xFFFFFFFEull || a.ntiles != p.ntiles || p.vfront != 0 || grid != p.grid)
+    return hipErrorInvalidValue;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.part) | reinterpret_cast<uintptr_t>(a.tables);
+  uint32_t covered = 0;  // every data column is a survivor or a reconstruct row's, once
+  for (int j = 0; j < a.k; ++j) {
+    if (!a.in[j] || a.surv_col[j] >= a.k) return hipErrorInvalidValue;
+    bits |= reinterpret_cast<uintptr_t>(a.in[j]);
+    if (a.surv_col[j] >= 0) covered ^= 1u << a.surv_col[j];
+  }
+  for (int r = 0; r < a.rows; ++r) {
+    if (a.row_col[r] < 0 || a.row_col[r] >= a.k) return hipErrorInvalidValue;
+    covered ^= 1u << a.row_col[r];
+  }
+  if (bits % 16 || covered != (a.k >= 32 ? ~0u : (1u << a.k) - 1u)) return hipErrorInvalidValue;
+  const dim3 g(static_cast<unsigned>(grid)), b(kCrcWgThreads);
+  if (a.rows) hipLaunchKernelGGL(sse_ec_read_kernel<true>, g, b, 0, s, a, t);
+  else hipLaunchKernelGGL(sse_ec_read_kernel<false>, g, b, 0, s, a, t);
   return hipGetLastError();
 }
 

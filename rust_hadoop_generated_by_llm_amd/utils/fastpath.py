@@ -163,6 +163,21 @@ class FastPathClient:
         st, _total, replicas, msg = self._call(14, body)
         return st, replicas if st == OK else 0, int(msg, 16) if st == OK else 0
 
+    def sse_ec_read(self, block_id: str, k: int, m: int, shard_len: int, size: int, locations: list[str],
+                    shm_path: str, shm_off: int, cap: int, key: bytes, request_id: str | None = None):
+        """GET of an SSE-S3 object held as an RS(k, m) file by one kernel on the chunkserver's GPU
+        (csrc/fastpath.cpp op 15): the surviving shards of ``block_id`` at ``locations`` ("" = lost) are
+        gathered into its HBM, lost columns rebuilt, and the plaintext of the ``size``-byte blob, and
+        nothing else, lands at ``shm_off`` of the client's arena. Returns (status, n): OK, AUTH_FAILED,
+        IO_ERROR, or UNSUPPORTED when the gather or the kernel would not take it (the caller then reads
+        and decrypts its own way)."""
+        body = struct.pack("<HHQQQQ", k, m, shard_len, size, shm_off, cap) + _s(block_id.encode()) + _s(key)
+        body += _s(shm_path.encode())
+        body += struct.pack("<H", len(locations)) + b"".join(_s(a.encode()) for a in locations)
+        body += _s(self._rid(request_id))
+        st, _total, n, _msg = self._call(15, body)
+        return st, n if st == OK else 0
+
     @staticmethod
     def _rid(request_id: str | None) -> bytes:
         from .rpc import current_request_id
